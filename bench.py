@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- ray-samples/sec of a full NeuralRecon-W train step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W         (N>1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]   (N>1: launched by torch.distributed.run)
 
 A "step" = NeuconWRenderer.render (sampler + background NeRF + SDF/colour nets + compositor)
 + NeuconWLoss + backward (incl. the second-order SDF terms and every weight gradient) + the
@@ -15,7 +15,11 @@ default: rendered outputs within 1e-4 of the oracle at initialisation AND at tra
 select the others, `plain_f16_mode` times the step without the split).  Rays
 shard across ranks (weak scaling); value = total ray-samples of all ranks / max-over-ranks time.
 
-Prints ONE JSON line (rank 0) with the driver contract keys plus
+A plain run sets up, warms up, times the K steps, writes --dump-outputs (the last timed step's loss, render outputs and
+updated parameters as DIR/<name>.npy) and prints ONE JSON line (rank 0) with the driver contract keys (`metric`, `value`,
+`unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...); the keys below and `allreduce` are null there.  Every warm-up and
+timed step starts from the initial weights and Adam moments (same work, same inputs; the last step's outputs are then
+reproducible from run to run, see make_step).  --full measures them as well:
   `roofline`     dominant kernel by HIP-event time: `frac_mfma` (algorithmic FLOPs / duration / 2.5 PFLOP/s)
                  AND `frac_hbm` (algorithmic stash bytes / duration / 8 TB/s) -- `frac` is the one for `bound`; `traffic`
                  = HBM bytes per launch MEASURED WITH THIS RUN (two rocprofv3 --pmc passes of a short re-run of this
@@ -694,6 +698,31 @@ def bench_render(args, nw, L, dev, world, rank):
             "chunk_4096_rays_value": 4096 * S / dt4, "traffic": traffic, "parity": parity, "roofline": None, "cpu_baseline": None}))
 
 
+def dump_outputs(path, last, train, budget=60e6):
+    """--dump-outputs: what the last timed step handed its caller -- the loss and the render outputs (TrainStep's return
+    values) and the flat parameters after the Adam step with the gradient they were updated from -- as <path>/<name>.npy,
+    float64 stays float64, everything else float32.  Arrays keep their shape; should they exceed `budget` bytes in all
+    (larger --rays), the largest ones are cut to a fixed seeded sample of their flattened elements (ascending index)."""
+    import numpy as np
+
+    arrs = {"loss": last["loss"]}
+    arrs.update((k, v) for k, v in last["out"].items() if torch.is_tensor(v))
+    arrs["params"], arrs["params_grad"] = train.fp.flat, train.fp.flat_grad
+    os.makedirs(path, exist_ok=True)
+    items = sorted(arrs.items(), key=lambda kv: (kv[1].numel(), kv[0]))
+    left = budget
+    for i, (name, v) in enumerate(items):
+        v = v.detach()
+        v = v.double() if v.dtype == torch.float64 else v.float()
+        cap = int(left / (len(items) - i)) // v.element_size()  # an equal share of what the smaller arrays left
+        if v.numel() > cap:
+            idx = torch.randperm(v.numel(), generator=torch.Generator().manual_seed(0))[:cap].sort().values
+            v = v.reshape(-1)[idx.to(v.device)]
+        a = v.cpu().numpy()
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
+
+
 def main():
     if len(sys.argv) == 3 and sys.argv[1] == "--allreduce-probe":
         return allreduce_probe(int(sys.argv[2]))
@@ -725,6 +754,15 @@ def main():
     ap.add_argument("--one-stream", action="store_true",
                     help="run the background NeRF's launches on the main stream too (NEUCONW_BG_STREAM=0): nothing overlaps, so a rocprofv3 "
                          "kernel trace of this run reproduces `per_step_kernel_ms` kernel by kernel (profiles/r06/bench_onestream_*)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the timed steps: per-kernel roofline (HIP events + the rocprofv3 --pmc passes), the "
+                         "all-reduce probe, the other precisions and modes (parity_mode, alt_mode, plain_f16_mode, bg_elimination), "
+                         "the CPU baseline and the measured parity of the timed batch.  Off: set up, warm up, time --steps steps, "
+                         "write --dump-outputs, print the line (those keys null)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy (float32 / float64): "
+                         "the loss, the render outputs and the updated flat parameters and their gradient (at most 64 MB in all); "
+                         "every step starts from the initial state, so two runs with the same arguments write the same arrays")
     ap.add_argument("--dist-check", action="store_true",
                     help="initialise the process group, print {world, ranks, devices} from rank 0 and exit (launcher test; "
                          "needs no GPU with NCW_DIST_BACKEND=gloo)")
@@ -826,8 +864,28 @@ def main():
         train_ = nw.TrainStep(rdr_, [emb_, neuconw_, nerf_], loss_fn, lr=1e-4 * world * R / 4096.0, eps=1e-7, clip=0.99,
                               world_size=world, capture=args.graph, capture_warmup=3)
 
-        def step_(i):
-            loss_, _ = train_(rays, ts, label, rgbs, background_rgb=bg, cos_anneal_ratio=min(1.0, i / 50000.0))
+        # Every step starts from the initial weights and optimiser moments: the same work on the same inputs each step.
+        # The 16-bit step sums its weight and appearance-code gradients with f32 atomics (last-bit differences from run to
+        # run); carried over a trajectory, Adam and the discrete sampler would grow them into different sample positions,
+        # so the outputs of a step that follows other steps are not reproducible.  From a fixed state they are (forward
+        # bitwise, gradients and updated weights to rounding), which --dump-outputs needs.
+        flat0 = train_.fp.flat.detach().clone()
+        opt_ = train_.opt
+
+        def reset_():
+            train_.fp.flat.data.copy_(flat0)
+            if hasattr(opt_, "exp_avg"):  # trainer.FlatAdam (device-resident moments; its step counters run on)
+                opt_.exp_avg.zero_()
+                opt_.exp_avg_sq.zero_()
+            else:  # stock torch.optim.Adam
+                opt_.state.clear()
+            train_.fp.mark_updated()
+
+        def step_(i, keep=None):
+            reset_()
+            loss_, out_ = train_(rays, ts, label, rgbs, background_rgb=bg, cos_anneal_ratio=min(1.0, i / 50000.0))
+            if keep is not None:  # --dump-outputs: the last timed step's outputs, as the caller of TrainStep receives them
+                keep.update(loss=loss_, out=out_)
             return loss_
 
         return step_, train_, (emb_, neuconw_, nerf_, rdr_)
@@ -845,9 +903,10 @@ def main():
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
+    last = {} if args.dump_outputs else None
     t0 = time.perf_counter()
     for i in range(args.steps):
-        loss = step(args.warmup + i)
+        loss = step(args.warmup + i, last if i == args.steps - 1 else None)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -872,26 +931,30 @@ def main():
         if world > 1:
             dist.destroy_process_group()
         return
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, train)
+    del last
 
     # ---- per-kernel HIP-event timing over a few more live steps (same stream) -> roofline ---------------
     roofline = None
     # every rank runs the same extra steps (the step contains the gradient all-reduce); only rank 0 records
     prof_steps = max(2, min(5, args.steps))
-    if rank == 0:
+    if rank == 0 and args.full:
         L.PROFILE = {}
     # The timed region above runs the background NeRF's launches on a second stream beside the SDF / colour chain
     # (renderer.use_bg_stream); an event pair around a launch that shares the device measures both chains.  The per-kernel
     # pass therefore runs the same steps on ONE stream: every duration below is the kernel's own (the dominant kernel, the
     # weight-gradient launch, runs alone in either form, so its duration is also what rocprofv3 reports for the timed region).
-    two_streams, rdr.use_bg_stream = rdr.use_bg_stream, False
-    for i in range(prof_steps):
-        train.eager_step(rays, ts, label, rgbs, background_rgb=bg,
-                         cos_anneal_ratio=min(1.0, (args.warmup + args.steps + i) / 50000.0))
-    torch.cuda.synchronize()
-    rdr.use_bg_stream = two_streams
-    if world > 1:
-        dist.barrier()
-    if rank == 0:
+    if args.full:
+        two_streams, rdr.use_bg_stream = rdr.use_bg_stream, False
+        for i in range(prof_steps):
+            train.eager_step(rays, ts, label, rgbs, background_rgb=bg,
+                             cos_anneal_ratio=min(1.0, (args.warmup + args.steps + i) / 50000.0))
+        torch.cuda.synchronize()
+        rdr.use_bg_stream = two_streams
+        if world > 1:
+            dist.barrier()
+    if rank == 0 and args.full:
         prof, L.PROFILE = L.PROFILE, None
         prof = {(k[:-4] if k.endswith("_f16") else k): v for k, v in prof.items()}  # the fp16 build of an entry point
         fl = kernel_flops(R)
@@ -971,25 +1034,26 @@ def main():
     # FlatParams.allreduce issues once per step).  At N = 1 a one-rank RCCL group is created just for this: it prices the
     # launch + the in-place kernel, not the wire; at N > 1 it is the real collective over xGMI (max over ranks).
     allreduce = None
-    try:
-        if world == 1 and not dist.is_initialized():
-            # a ONE-rank RCCL group, in a child process with a hard time limit: a backend that cannot come up on this box
-            # must cost the bench line a null, never a hang
-            import subprocess
+    if args.full:
+        try:
+            if world == 1 and not dist.is_initialized():
+                # a ONE-rank RCCL group, in a child process with a hard time limit: a backend that cannot come up on this box
+                # must cost the bench line a null, never a hang
+                import subprocess
 
-            r_ = subprocess.run([sys.executable, os.path.abspath(__file__), "--allreduce-probe", str(train.fp.flat_grad.numel())],
-                                capture_output=True, text=True, timeout=90, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
-            ls_ = [l for l in r_.stdout.splitlines() if l.startswith("{")]
-            allreduce = json.loads(ls_[-1]) if ls_ else {"allreduce_ms": None, "error": (r_.stderr or r_.stdout)[-300:]}
-        else:
-            allreduce = time_allreduce(train.fp.flat_grad.numel(), dev, world)
-    except Exception as e:  # never take the bench line down
-        allreduce = {"allreduce_ms": None, "error": "%r" % (e,)}
+                r_ = subprocess.run([sys.executable, os.path.abspath(__file__), "--allreduce-probe", str(train.fp.flat_grad.numel())],
+                                    capture_output=True, text=True, timeout=90, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
+                ls_ = [l for l in r_.stdout.splitlines() if l.startswith("{")]
+                allreduce = json.loads(ls_[-1]) if ls_ else {"allreduce_ms": None, "error": (r_.stderr or r_.stdout)[-300:]}
+            else:
+                allreduce = time_allreduce(train.fp.flat_grad.numel(), dev, world)
+        except Exception as e:  # never take the bench line down
+            allreduce = {"allreduce_ms": None, "error": "%r" % (e,)}
 
     # ---- the fp32 parity mode (the <= 1e-4 mode, tests/test_gpu_render.py) timed in the same process ---------------
     parity = None
     alt = elim = plain = None
-    if not args.no_parity_mode and args.prec in ("bf16", "f16") and not args.graph:
+    if args.full and not args.no_parity_mode and args.prec in ("bf16", "f16") and not args.graph:
         del train, step
         torch.cuda.empty_cache()
         alt_name = "bf16" if args.prec == "f16" else "f16"
@@ -1071,7 +1135,7 @@ def main():
 
     cpu = None
     parity_obj = None
-    if rank == 0 and not args.no_cpu_baseline:  # N > 1: rank 0 alone (the other ranks wait at the barrier below)
+    if rank == 0 and args.full and not args.no_cpu_baseline:  # N > 1: rank 0 alone (the other ranks wait at the barrier below)
         try:
             cpu, ref32 = cpu_baseline()
         except Exception as e:  # the baseline must never take the bench line down
@@ -1131,7 +1195,7 @@ def main():
             except Exception as e:
                 parity_obj = {"dtype": args.prec, "error": "failed: %r" % (e,)}
 
-    if world > 1:
+    if world > 1 and args.full:
         dist.barrier()  # rank 0's CPU-baseline / parity / PMC legs are over
     if rank == 0:
         names = {"headline": "BASELINE.json configs[1]", "shipped": "shipped yaml shape, secondary",

@@ -8,7 +8,7 @@ for tag in tags:
     env = dict(os.environ)
     if tag not in ("", "default"):
         env["NEUCONW_HIP_LIB"] = os.path.join(ROOT, "neuralrecon-w_amd", "libneuconw_hip_%s.so" % tag)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")]
     if not line:

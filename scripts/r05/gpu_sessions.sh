@@ -13,14 +13,14 @@ T="timeout -k 10"
 $T 900 python -m pytest tests -m gpu -q --timeout 500 -x > $OUT/full.log 2>&1; echo "pytest -m gpu rc $?" >> $OUT/status
 $T 900 python -m pytest tests/test_gpu_render_only.py tests/test_gpu_voxel.py tests/test_gpu_grid.py tests/test_gpu_fullsize.py tests/test_gpu_trainer.py -m gpu -q --timeout 500 -s > $OUT/new_tests.log 2>&1; echo "new tests rc $?" >> $OUT/status
 $T 120 python __graft_entry__.py --smoke > $OUT/smoke.log 2>&1; echo "smoke rc $?" >> $OUT/status
-$T 400 python bench.py --save-trained-state $OUT/trained_state_bench.pt > $OUT/bench_v1.json 2> $OUT/bench_v1.err; echo "bench rc $?" >> $OUT/status
-$T 300 python bench.py --config render > $OUT/bench_render.json 2> $OUT/bench_render.err; echo "render rc $?" >> $OUT/status
-$T 300 python bench.py --config render --bg-eliminate --no-pmc > $OUT/bench_render_elim.json 2> $OUT/bench_render_elim.err; echo "render elim rc $?" >> $OUT/status
-$T 300 python bench.py --config voxel --no-pmc > $OUT/bench_voxel.json 2> $OUT/bench_voxel.err; echo "voxel rc $?" >> $OUT/status
-$T 300 python bench.py --config grid512 --prec f16 > $OUT/bench_grid512_f16.json 2> $OUT/bench_grid512.err; echo "grid512 rc $?" >> $OUT/status
+$T 400 python bench.py --full --save-trained-state $OUT/trained_state_bench.pt > $OUT/bench_v1.json 2> $OUT/bench_v1.err; echo "bench rc $?" >> $OUT/status
+$T 300 python bench.py --full --config render > $OUT/bench_render.json 2> $OUT/bench_render.err; echo "render rc $?" >> $OUT/status
+$T 300 python bench.py --full --config render --bg-eliminate --no-pmc > $OUT/bench_render_elim.json 2> $OUT/bench_render_elim.err; echo "render elim rc $?" >> $OUT/status
+$T 300 python bench.py --full --config voxel --no-pmc > $OUT/bench_voxel.json 2> $OUT/bench_voxel.err; echo "voxel rc $?" >> $OUT/status
+$T 300 python bench.py --full --config grid512 --prec f16 > $OUT/bench_grid512_f16.json 2> $OUT/bench_grid512.err; echo "grid512 rc $?" >> $OUT/status
 for i in 1 2 3; do
-  $T 200 python bench.py --config shipped --no-pmc --no-cpu-baseline --no-parity-mode > $OUT/shipped_dense_$i.json 2>/dev/null; echo "shipped dense $i rc $?" >> $OUT/status
-  $T 200 python bench.py --config shipped --no-pmc --no-cpu-baseline --no-parity-mode --bg-eliminate > $OUT/shipped_elim_$i.json 2>/dev/null; echo "shipped elim $i rc $?" >> $OUT/status
+  $T 200 python bench.py --full --config shipped --no-pmc --no-cpu-baseline --no-parity-mode > $OUT/shipped_dense_$i.json 2>/dev/null; echo "shipped dense $i rc $?" >> $OUT/status
+  $T 200 python bench.py --full --config shipped --no-pmc --no-cpu-baseline --no-parity-mode --bg-eliminate > $OUT/shipped_elim_$i.json 2>/dev/null; echo "shipped elim $i rc $?" >> $OUT/status
 done
 $T 120 scripts/probes/atomic_probe > $OUT/atomic_probe.log 2>&1; echo "atomic probe rc $?" >> $OUT/status
 PORT=$((20000 + RANDOM % 20000))
@@ -36,17 +36,17 @@ s2() {
 OUT=gpurun_out/r05b; mkdir -p $OUT; rm -f $OUT/status
 T="timeout -k 10"
 $T 600 python -m pytest tests/test_gpu_render_only.py tests/test_gpu_voxel.py tests/test_gpu_fullsize.py tests/test_gpu_sdf.py tests/test_gpu_sdf_train.py tests/test_gpu_bg_select.py tests/test_gpu_trainer.py -m gpu -q --timeout 500 -s > $OUT/tests.log 2>&1; echo "tests rc $?" >> $OUT/status
-$T 400 python bench.py --no-pmc > $OUT/bench_v2.json 2> $OUT/bench_v2.err; echo "bench rc $?" >> $OUT/status
-NEUCONW_SDF_ADJ_SPLIT=0 $T 300 python bench.py --no-pmc --no-cpu-baseline --no-parity-mode > $OUT/bench_v2_adj_off.json 2>/dev/null; echo "bench adj off rc $?" >> $OUT/status
+$T 400 python bench.py --full --no-pmc > $OUT/bench_v2.json 2> $OUT/bench_v2.err; echo "bench rc $?" >> $OUT/status
+NEUCONW_SDF_ADJ_SPLIT=0 $T 300 python bench.py --full --no-pmc --no-cpu-baseline --no-parity-mode > $OUT/bench_v2_adj_off.json 2>/dev/null; echo "bench adj off rc $?" >> $OUT/status
 for i in 1 2; do
-  $T 200 python bench.py --config shipped --no-pmc --no-cpu-baseline --no-parity-mode > $OUT/shipped_dense_$i.json 2>/dev/null; echo "shipped dense $i rc $?" >> $OUT/status
-  $T 200 python bench.py --config shipped --no-pmc --no-cpu-baseline --no-parity-mode --bg-eliminate > $OUT/shipped_elim_$i.json 2>/dev/null; echo "shipped elim $i rc $?" >> $OUT/status
+  $T 200 python bench.py --full --config shipped --no-pmc --no-cpu-baseline --no-parity-mode > $OUT/shipped_dense_$i.json 2>/dev/null; echo "shipped dense $i rc $?" >> $OUT/status
+  $T 200 python bench.py --full --config shipped --no-pmc --no-cpu-baseline --no-parity-mode --bg-eliminate > $OUT/shipped_elim_$i.json 2>/dev/null; echo "shipped elim $i rc $?" >> $OUT/status
 done
 for W in 256 384 512 640 1024; do
-  NCW_WGRAD_TARGET_WGS=$W $T 200 python bench.py --config shipped --no-pmc --no-cpu-baseline --no-parity-mode --bg-eliminate > $OUT/shipped_elim_wgs$W.json 2>/dev/null; echo "shipped elim wgs $W rc $?" >> $OUT/status
-  NCW_WGRAD_TARGET_WGS=$W $T 200 python bench.py --config shipped --no-pmc --no-cpu-baseline --no-parity-mode > $OUT/shipped_dense_wgs$W.json 2>/dev/null; echo "shipped dense wgs $W rc $?" >> $OUT/status
+  NCW_WGRAD_TARGET_WGS=$W $T 200 python bench.py --full --config shipped --no-pmc --no-cpu-baseline --no-parity-mode --bg-eliminate > $OUT/shipped_elim_wgs$W.json 2>/dev/null; echo "shipped elim wgs $W rc $?" >> $OUT/status
+  NCW_WGRAD_TARGET_WGS=$W $T 200 python bench.py --full --config shipped --no-pmc --no-cpu-baseline --no-parity-mode > $OUT/shipped_dense_wgs$W.json 2>/dev/null; echo "shipped dense wgs $W rc $?" >> $OUT/status
 done
-$T 200 python bench.py --no-pmc --no-cpu-baseline --no-parity-mode --bg-eliminate > $OUT/headline_elim.json 2>/dev/null; echo "headline elim rc $?" >> $OUT/status
+$T 200 python bench.py --full --no-pmc --no-cpu-baseline --no-parity-mode --bg-eliminate > $OUT/headline_elim.json 2>/dev/null; echo "headline elim rc $?" >> $OUT/status
 cat $OUT/status; grep -E "passed|failed" $OUT/tests.log | tail -2; grep -E "^FAILED|^ERROR" $OUT/tests.log | head
 }
 
@@ -58,11 +58,11 @@ T="timeout -k 10"
 NEUCONW_HIP_LIB=neuralrecon-w_amd/libneuconw_hip_nb2.so $T 300 python scripts/diag/pp_nb2.py > $OUT/pp_nb2.log 2>&1; echo "pp_nb2 rc $?" >> $OUT/status
 $T 900 python -m pytest tests -m gpu -q --timeout 500 > $OUT/full.log 2>&1; echo "pytest -m gpu rc $?" >> $OUT/status
 for OP in 1.0 1.3 1.6 2.0 2.5; do
-  NCW_SEL_OVERPLAN=$OP $T 200 python bench.py --no-pmc --no-cpu-baseline --no-parity-mode --bg-eliminate > $OUT/headline_elim_op$OP.json 2>/dev/null; echo "headline elim op $OP rc $?" >> $OUT/status
-  NCW_SEL_OVERPLAN=$OP $T 200 python bench.py --config shipped --no-pmc --no-cpu-baseline --no-parity-mode --bg-eliminate > $OUT/shipped_elim_op$OP.json 2>/dev/null; echo "shipped elim op $OP rc $?" >> $OUT/status
+  NCW_SEL_OVERPLAN=$OP $T 200 python bench.py --full --no-pmc --no-cpu-baseline --no-parity-mode --bg-eliminate > $OUT/headline_elim_op$OP.json 2>/dev/null; echo "headline elim op $OP rc $?" >> $OUT/status
+  NCW_SEL_OVERPLAN=$OP $T 200 python bench.py --full --config shipped --no-pmc --no-cpu-baseline --no-parity-mode --bg-eliminate > $OUT/shipped_elim_op$OP.json 2>/dev/null; echo "shipped elim op $OP rc $?" >> $OUT/status
 done
 for i in 1 2 3; do
-  $T 200 python bench.py --config shipped --no-pmc --no-cpu-baseline --no-parity-mode --graph > $OUT/shipped_dense_graph_$i.json 2>/dev/null; echo "shipped dense graph $i rc $?" >> $OUT/status
+  $T 200 python bench.py --full --config shipped --no-pmc --no-cpu-baseline --no-parity-mode --graph > $OUT/shipped_dense_graph_$i.json 2>/dev/null; echo "shipped dense graph $i rc $?" >> $OUT/status
 done
 cat $OUT/status; grep -E "passed|failed" $OUT/full.log | tail -2; grep -E "^FAILED|^ERROR" $OUT/full.log | head; cat $OUT/pp_nb2.log
 }
@@ -73,8 +73,8 @@ s4() {
 OUT=gpurun_out/r05d; mkdir -p $OUT; rm -f $OUT/status
 T="timeout -k 10"
 for i in 1 2; do
-  $T 200 python bench.py --no-pmc --no-cpu-baseline --no-parity-mode > $OUT/headline_$i.json 2>/dev/null; echo "headline $i rc $?" >> $OUT/status
-  NEUCONW_HIP_LIB=neuralrecon-w_amd/libneuconw_hip_wst.so $T 200 python bench.py --no-pmc --no-cpu-baseline --no-parity-mode > $OUT/headline_wst_$i.json 2>/dev/null; echo "headline wst $i rc $?" >> $OUT/status
+  $T 200 python bench.py --full --no-pmc --no-cpu-baseline --no-parity-mode > $OUT/headline_$i.json 2>/dev/null; echo "headline $i rc $?" >> $OUT/status
+  NEUCONW_HIP_LIB=neuralrecon-w_amd/libneuconw_hip_wst.so $T 200 python bench.py --full --no-pmc --no-cpu-baseline --no-parity-mode > $OUT/headline_wst_$i.json 2>/dev/null; echo "headline wst $i rc $?" >> $OUT/status
 done
 export TMPDIR=/tmp
 for NB in 1 2; do
@@ -106,10 +106,10 @@ s5() {
 OUT=gpurun_out/r05e; mkdir -p $OUT; rm -f $OUT/status
 T="timeout -k 10"
 $T 900 python -m pytest tests -m gpu -q --timeout 500 > $OUT/full.log 2>&1; echo "pytest -m gpu rc $?" >> $OUT/status
-$T 400 python bench.py --config shipped --no-pmc > $OUT/bench_shipped.json 2> $OUT/bench_shipped.err; echo "shipped rc $?" >> $OUT/status
-NEUCONW_SDF_ADJ_SPLIT=0 $T 300 python bench.py --config shipped --no-pmc --no-cpu-baseline --no-parity-mode > $OUT/bench_shipped_adj_off.json 2>/dev/null; echo "shipped adj off rc $?" >> $OUT/status
-$T 300 python bench.py --config shipped --no-pmc --no-cpu-baseline --no-parity-mode --bg-eliminate > $OUT/bench_shipped_elim.json 2>/dev/null; echo "shipped elim rc $?" >> $OUT/status
-$T 300 python bench.py --config shipped --no-pmc --no-cpu-baseline --no-parity-mode > $OUT/bench_shipped_2.json 2>/dev/null; echo "shipped 2 rc $?" >> $OUT/status
+$T 400 python bench.py --full --config shipped --no-pmc > $OUT/bench_shipped.json 2> $OUT/bench_shipped.err; echo "shipped rc $?" >> $OUT/status
+NEUCONW_SDF_ADJ_SPLIT=0 $T 300 python bench.py --full --config shipped --no-pmc --no-cpu-baseline --no-parity-mode > $OUT/bench_shipped_adj_off.json 2>/dev/null; echo "shipped adj off rc $?" >> $OUT/status
+$T 300 python bench.py --full --config shipped --no-pmc --no-cpu-baseline --no-parity-mode --bg-eliminate > $OUT/bench_shipped_elim.json 2>/dev/null; echo "shipped elim rc $?" >> $OUT/status
+$T 300 python bench.py --full --config shipped --no-pmc --no-cpu-baseline --no-parity-mode > $OUT/bench_shipped_2.json 2>/dev/null; echo "shipped 2 rc $?" >> $OUT/status
 cat $OUT/status; grep -E "passed|failed" $OUT/full.log | tail -2; grep -E "^FAILED|^ERROR" $OUT/full.log | head
 }
 
@@ -121,7 +121,7 @@ T="timeout -k 10"
 $T 900 python -m pytest tests -m gpu -q --timeout 500 > $OUT/full.log 2>&1; echo "pytest -m gpu rc $?" >> $OUT/status
 $T 300 python -m pytest tests/test_gpu_sdf.py tests/test_gpu_edges.py -m gpu -q -s -k "adjoint or 512" > $OUT/new_tests.log 2>&1; echo "new tests rc $?" >> $OUT/status
 $T 100 python __graft_entry__.py --smoke > $OUT/smoke.log 2>&1; echo "smoke rc $?" >> $OUT/status
-$T 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_cmd.json 2> $OUT/bench.err; echo "bench rc $?" >> $OUT/status
+$T 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_cmd.json 2> $OUT/bench.err; echo "bench rc $?" >> $OUT/status
 cat $OUT/status; grep -E "passed|failed" $OUT/full.log | tail -2; grep -E "^FAILED|^ERROR" $OUT/full.log | head; grep -E "normals vs fp64|samples per ray" $OUT/new_tests.log
 }
 
@@ -132,10 +132,10 @@ OUT=gpurun_out/r05k; mkdir -p $OUT; rm -f $OUT/status
 T="timeout -k 10"
 $T 600 python -m pytest tests/test_gpu_bg_select.py tests/test_gpu_color_nerf.py tests/test_gpu_fullsize.py tests/test_gpu_render_only.py tests/test_gpu_trainer.py tests/test_gpu_voxel.py -m gpu -q --timeout 500 -s > $OUT/tests.log 2>&1; echo "tests rc $?" >> $OUT/status
 for S in 1000 2000 3000 4000; do
-  $T 200 python bench.py --seed $S --no-pmc --no-parity-mode > $OUT/bench_seed$S.json 2>/dev/null; echo "seed $S rc $?" >> $OUT/status
+  $T 200 python bench.py --full --seed $S --no-pmc --no-parity-mode > $OUT/bench_seed$S.json 2>/dev/null; echo "seed $S rc $?" >> $OUT/status
 done
-NEUCONW_NERF_REFINE=0 $T 200 python bench.py --no-pmc --no-cpu-baseline --no-parity-mode > $OUT/bench_refine_off.json 2>/dev/null; echo "refine off rc $?" >> $OUT/status
-$T 200 python bench.py --no-pmc --no-cpu-baseline --no-parity-mode --bg-eliminate > $OUT/bench_elim.json 2>/dev/null; echo "elim rc $?" >> $OUT/status
+NEUCONW_NERF_REFINE=0 $T 200 python bench.py --full --no-pmc --no-cpu-baseline --no-parity-mode > $OUT/bench_refine_off.json 2>/dev/null; echo "refine off rc $?" >> $OUT/status
+$T 200 python bench.py --full --no-pmc --no-cpu-baseline --no-parity-mode --bg-eliminate > $OUT/bench_elim.json 2>/dev/null; echo "elim rc $?" >> $OUT/status
 cat $OUT/status; grep -E "passed|failed" $OUT/tests.log | tail -2; grep -E "^FAILED|^ERROR" $OUT/tests.log | head; grep -E "background NeRF at the" $OUT/tests.log
 }
 
@@ -146,11 +146,11 @@ OUT=gpurun_out/r05l; mkdir -p $OUT; rm -f $OUT/status
 T="timeout -k 10"
 $T 700 python -m pytest tests/test_gpu_bg_select.py tests/test_gpu_color_nerf.py tests/test_gpu_fullsize.py tests/test_gpu_render_only.py tests/test_gpu_voxel.py tests/test_gpu_grid.py tests/test_gpu_render.py -m gpu -q --timeout 600 -s > $OUT/tests.log 2>&1; echo "tests rc $?" >> $OUT/status
 for S in 1000 2000 3000 4000; do
-  $T 200 python bench.py --seed $S --no-pmc --no-parity-mode > $OUT/bench_seed$S.json 2>/dev/null; echo "seed $S rc $?" >> $OUT/status
+  $T 200 python bench.py --full --seed $S --no-pmc --no-parity-mode > $OUT/bench_seed$S.json 2>/dev/null; echo "seed $S rc $?" >> $OUT/status
 done
-$T 200 python bench.py --no-pmc --no-cpu-baseline --no-parity-mode --bg-eliminate > $OUT/bench_elim.json 2>/dev/null; echo "elim rc $?" >> $OUT/status
+$T 200 python bench.py --full --no-pmc --no-cpu-baseline --no-parity-mode --bg-eliminate > $OUT/bench_elim.json 2>/dev/null; echo "elim rc $?" >> $OUT/status
 export TMPDIR=/tmp
-$T 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o k -- python bench.py --inner --no-pmc --no-cpu-baseline --no-parity-mode > $OUT/prof_bench.json 2> $OUT/prof.err; echo "prof rc $?" >> $OUT/status
+$T 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o k -- python bench.py --full --inner --no-pmc --no-cpu-baseline --no-parity-mode > $OUT/prof_bench.json 2> $OUT/prof.err; echo "prof rc $?" >> $OUT/status
 find $OUT/prof -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats.csv \;
 rm -rf $OUT/prof
 cat $OUT/status; grep -E "passed|failed" $OUT/tests.log | tail -2; grep -E "^FAILED|^ERROR" $OUT/tests.log | head; grep -E "background NeRF at the" $OUT/tests.log
@@ -164,9 +164,9 @@ OUT=gpurun_out/r05m; mkdir -p $OUT; rm -f $OUT/status
 T="timeout -k 10"
 $T 700 python -m pytest tests/test_gpu_trainer.py tests/test_gpu_fullsize.py tests/test_gpu_repro.py tests/test_gpu_train_driver.py tests/test_gpu_ddp.py tests/test_gpu_rccl_world1.py tests/test_gpu_render_only.py -m gpu -q --timeout 600 -s > $OUT/tests.log 2>&1; echo "tests rc $?" >> $OUT/status
 for I in 1 2 3; do
-  $T 200 python bench.py --no-pmc --no-parity-mode --no-cpu-baseline > $OUT/bench_$I.json 2>/dev/null; echo "bench $I rc $?" >> $OUT/status
+  $T 200 python bench.py --full --no-pmc --no-parity-mode --no-cpu-baseline > $OUT/bench_$I.json 2>/dev/null; echo "bench $I rc $?" >> $OUT/status
 done
-$T 200 python bench.py --no-pmc --no-cpu-baseline --no-parity-mode --bg-eliminate > $OUT/bench_elim.json 2>/dev/null; echo "elim rc $?" >> $OUT/status
+$T 200 python bench.py --full --no-pmc --no-cpu-baseline --no-parity-mode --bg-eliminate > $OUT/bench_elim.json 2>/dev/null; echo "elim rc $?" >> $OUT/status
 cat $OUT/status; grep -E "passed|failed" $OUT/tests.log | tail -2; grep -E "^FAILED|^ERROR" $OUT/tests.log | head
 python - <<'P'
 import json,glob
@@ -182,13 +182,13 @@ s10() {
 OUT=gpurun_out/r05n; mkdir -p $OUT; rm -f $OUT/status
 T="timeout -k 10"
 export TMPDIR=/tmp
-$T 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/prof -o k -- python bench.py --inner --no-pmc --no-cpu-baseline --no-parity-mode > $OUT/prof_bench.json 2> $OUT/prof.err; echo "prof rc $?" >> $OUT/status
+$T 300 rocprofv3 --kernel-trace --output-format csv -d $OUT/prof -o k -- python bench.py --full --inner --no-pmc --no-cpu-baseline --no-parity-mode > $OUT/prof_bench.json 2> $OUT/prof.err; echo "prof rc $?" >> $OUT/status
 find $OUT/prof -name "*kernel_trace.csv" -exec cp {} $OUT/kernel_trace.csv \;
 rm -rf $OUT/prof
 python scripts/diag/trace_gaps.py $OUT/kernel_trace.csv > $OUT/trace_gaps.log 2>&1; echo "gaps rc $?" >> $OUT/status
 rm -f $OUT/kernel_trace.csv
-$T 200 python bench.py --graph --no-pmc --no-parity-mode --no-cpu-baseline > $OUT/bench_graph.json 2>$OUT/graph.err; echo "graph rc $?" >> $OUT/status
-$T 200 python bench.py --no-pmc --no-parity-mode --no-cpu-baseline > $OUT/bench_eager.json 2>/dev/null; echo "eager rc $?" >> $OUT/status
+$T 200 python bench.py --full --graph --no-pmc --no-parity-mode --no-cpu-baseline > $OUT/bench_graph.json 2>$OUT/graph.err; echo "graph rc $?" >> $OUT/status
+$T 200 python bench.py --full --no-pmc --no-parity-mode --no-cpu-baseline > $OUT/bench_eager.json 2>/dev/null; echo "eager rc $?" >> $OUT/status
 cat $OUT/status; cat $OUT/trace_gaps.log | tail -60
 python - <<'P'
 import json
@@ -217,7 +217,7 @@ $T 400 python -m pytest tests/test_gpu_bg_select.py tests/test_gpu_render_only.p
 for I in 1 2; do
 for V in main q44 q28 old; do
   if [ $V = main ]; then unset NEUCONW_HIP_LIB; else export NEUCONW_HIP_LIB=$PWD/neuralrecon-w_amd/libneuconw_hip_$V.so; fi
-  $T 200 python bench.py --no-pmc --no-parity-mode --no-cpu-baseline > $OUT/bench_${V}_$I.json 2>/dev/null; echo "bench $V $I rc $?" >> $OUT/status
+  $T 200 python bench.py --full --no-pmc --no-parity-mode --no-cpu-baseline > $OUT/bench_${V}_$I.json 2>/dev/null; echo "bench $V $I rc $?" >> $OUT/status
 done
 done
 unset NEUCONW_HIP_LIB
@@ -239,7 +239,7 @@ $T 400 python -m pytest tests/test_gpu_bg_select.py tests/test_gpu_render_only.p
 for I in 1 2; do
 for V in main g10 old; do
   if [ $V = main ]; then unset NEUCONW_HIP_LIB; else export NEUCONW_HIP_LIB=$PWD/neuralrecon-w_amd/libneuconw_hip_$V.so; fi
-  $T 200 python bench.py --no-pmc --no-parity-mode --no-cpu-baseline > $OUT/bench_${V}_$I.json 2>/dev/null; echo "bench $V $I rc $?" >> $OUT/status
+  $T 200 python bench.py --full --no-pmc --no-parity-mode --no-cpu-baseline > $OUT/bench_${V}_$I.json 2>/dev/null; echo "bench $V $I rc $?" >> $OUT/status
 done
 done
 unset NEUCONW_HIP_LIB
@@ -266,9 +266,9 @@ OUT=gpurun_out/r05s; mkdir -p $OUT; rm -f $OUT/status
 T="timeout -k 10"
 $T 700 python -m pytest tests/test_gpu_bg_select.py tests/test_gpu_render.py tests/test_gpu_render_only.py tests/test_gpu_fullsize.py tests/test_gpu_repro.py tests/test_gpu_trainer.py tests/test_gpu_voxel.py tests/test_gpu_edges.py -m gpu -q --timeout 600 > $OUT/tests.log 2>&1; echo "tests rc $?" >> $OUT/status
 for I in 1 2 3; do
-  $T 200 python bench.py --no-pmc --no-parity-mode --no-cpu-baseline > $OUT/bench_$I.json 2>/dev/null; echo "bench $I rc $?" >> $OUT/status
+  $T 200 python bench.py --full --no-pmc --no-parity-mode --no-cpu-baseline > $OUT/bench_$I.json 2>/dev/null; echo "bench $I rc $?" >> $OUT/status
 done
-NEUCONW_BG_STREAM=0 $T 200 python bench.py --no-pmc --no-parity-mode --no-cpu-baseline > $OUT/bench_one_stream.json 2>/dev/null; echo "one stream rc $?" >> $OUT/status
+NEUCONW_BG_STREAM=0 $T 200 python bench.py --full --no-pmc --no-parity-mode --no-cpu-baseline > $OUT/bench_one_stream.json 2>/dev/null; echo "one stream rc $?" >> $OUT/status
 cat $OUT/status; grep -E "passed|failed" $OUT/tests.log | tail -2; grep -E "^FAILED|^ERROR" $OUT/tests.log | head
 python - <<'P'
 import json,glob
@@ -289,7 +289,7 @@ grep -E "^variance" $OUT/sampler_split.log
 s17() {
 OUT=gpurun_out/r05u; mkdir -p $OUT; rm -f $OUT/status
 for S in 5000 6000 7000 8000 9000 10000; do
-  timeout -k 10 200 python bench.py --seed $S --no-pmc --no-parity-mode > $OUT/bench_seed$S.json 2>/dev/null; echo "seed $S rc $?" >> $OUT/status
+  timeout -k 10 200 python bench.py --full --seed $S --no-pmc --no-parity-mode > $OUT/bench_seed$S.json 2>/dev/null; echo "seed $S rc $?" >> $OUT/status
 done
 cat $OUT/status
 python - <<'P'
@@ -304,7 +304,7 @@ P
 s18() {
 OUT=gpurun_out/r05v; mkdir -p $OUT
 for S in 5000 10000; do
-  timeout -k 10 200 python bench.py --seed $S --no-pmc --no-parity-mode --save-trained-state $OUT/trained_seed$S.pt > $OUT/bench_seed$S.json 2>/dev/null; echo "seed $S rc $?"
+  timeout -k 10 200 python bench.py --full --seed $S --no-pmc --no-parity-mode --save-trained-state $OUT/trained_seed$S.pt > $OUT/bench_seed$S.json 2>/dev/null; echo "seed $S rc $?"
 done
 ls -la $OUT
 }

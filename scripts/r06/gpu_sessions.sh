@@ -6,13 +6,13 @@ cd "$(dirname "$0")/../.."
 NAME=${1:?session name}
 OUT=gpurun_out/r06_$NAME; mkdir -p $OUT
 export TMPDIR=/tmp
-B="python bench.py --no-pmc --no-parity-mode --no-cpu-baseline"
+B="python bench.py --full --no-pmc --no-parity-mode --no-cpu-baseline"
 
 s1() {  # trained-weights parity point of the SHIPPED shape for the CPU emulation; config 4's whole batch on one GPU; training equivalence
   for S in 1000 2000 3000; do
     timeout -k 10 300 $B --config shipped --seed $S --save-trained-state $OUT/trained_shipped_seed$S.pt > $OUT/bench_shipped_seed$S.json 2>$OUT/bench_shipped_seed$S.err; echo "shipped seed $S rc $?"
   done
-  timeout -k 10 400 python bench.py --rays 8192 --no-pmc > $OUT/bench_rays8192.json 2>$OUT/bench_rays8192.err; echo "rays 8192 rc $?"
+  timeout -k 10 400 python bench.py --full --rays 8192 --no-pmc > $OUT/bench_rays8192.json 2>$OUT/bench_rays8192.err; echo "rays 8192 rc $?"
   for N in 1500 3000; do
     timeout -k 10 600 python scripts/diag/train_equivalence.py --steps $N --precs f32,f32b,f16,f16_noextras --out $OUT/train_equivalence_$N.json > $OUT/train_equivalence_$N.log 2>&1; echo "train_equivalence $N rc $?"
   done
@@ -20,7 +20,7 @@ s1() {  # trained-weights parity point of the SHIPPED shape for the CPU emulatio
 
 s2() {  # (s1 skipped the parity legs with --no-cpu-baseline: the trained state is written by the parity leg)
   for S in 1000 2000 3000; do
-    timeout -k 10 400 python bench.py --no-pmc --no-parity-mode --config shipped --seed $S --save-trained-state $OUT/trained_shipped_seed$S.pt > $OUT/bench_shipped_seed$S.json 2>$OUT/bench_shipped_seed$S.err; echo "shipped seed $S rc $?"
+    timeout -k 10 400 python bench.py --full --no-pmc --no-parity-mode --config shipped --seed $S --save-trained-state $OUT/trained_shipped_seed$S.pt > $OUT/bench_shipped_seed$S.json 2>$OUT/bench_shipped_seed$S.err; echo "shipped seed $S rc $?"
   done
 }
 
@@ -34,12 +34,12 @@ s4() {  # W = 512: adjoint sweep with both operands as pairs + colour activation
   timeout -k 10 900 python -m pytest tests/test_gpu_voxel.py tests/test_gpu_sdf.py tests/test_gpu_color_nerf.py -x -q -s > $OUT/unit_tests.log 2>&1; echo "unit tests rc $?"; tail -3 $OUT/unit_tests.log
   timeout -k 10 900 python -m pytest tests/test_gpu_fullsize.py tests/test_gpu_render_only.py -x -q -s > $OUT/fullsize_tests.log 2>&1; echo "fullsize tests rc $?"; tail -3 $OUT/fullsize_tests.log
   for S in 1000 3000 4000 5000; do
-    timeout -k 10 400 python bench.py --no-pmc --no-parity-mode --config shipped --seed $S > $OUT/bench_shipped_seed$S.json 2>$OUT/bench_shipped_seed$S.err; echo "shipped seed $S rc $?"
+    timeout -k 10 400 python bench.py --full --no-pmc --no-parity-mode --config shipped --seed $S > $OUT/bench_shipped_seed$S.json 2>$OUT/bench_shipped_seed$S.err; echo "shipped seed $S rc $?"
   done
   NEUCONW_SDF_ADJ_SPLIT=0 NEUCONW_COLOR_ASPLIT=0 timeout -k 10 400 $B --config shipped > $OUT/bench_shipped_r5_kernels.json 2>/dev/null; echo "shipped, round-5 kernels rc $?"
   NEUCONW_SDF_ADJ_SPLIT=2 NEUCONW_COLOR_ASPLIT=0 timeout -k 10 400 $B --config shipped > $OUT/bench_shipped_adj2_only.json 2>/dev/null; echo "shipped, adj 2 only rc $?"
   NEUCONW_SDF_ADJ_SPLIT=0 NEUCONW_COLOR_ASPLIT=1 timeout -k 10 400 $B --config shipped > $OUT/bench_shipped_asplit_only.json 2>/dev/null; echo "shipped, act_split only rc $?"
-  NEUCONW_COLOR_ASPLIT=1 timeout -k 10 400 python bench.py --no-pmc --no-parity-mode > $OUT/bench_headline_asplit.json 2>/dev/null; echo "headline + act_split rc $?"
+  NEUCONW_COLOR_ASPLIT=1 timeout -k 10 400 python bench.py --full --no-pmc --no-parity-mode > $OUT/bench_headline_asplit.json 2>/dev/null; echo "headline + act_split rc $?"
   timeout -k 10 400 $B > $OUT/bench_headline.json 2>/dev/null; echo "headline rc $?"
 }
 
@@ -65,16 +65,16 @@ s8() {  # after pinning the hi / lo conversions (ncw_split8): the bisect again, 
   timeout -k 10 300 python scripts/diag/tunits_check.py > $OUT/tunits_check.log 2>&1; echo "tunits_check rc $?"; grep "f16 split" $OUT/tunits_check.log
   timeout -k 10 1500 python -m pytest tests -m gpu -q -s -p no:cacheprovider > $OUT/tests.log 2>&1; echo "tests rc $?"; tail -8 $OUT/tests.log
   timeout -k 10 600 python scripts/diag/sdf_infer_units.py --pmc > $OUT/sdf_infer_units.log 2>&1; echo "sdf_infer_units rc $?"
-  timeout -k 10 400 python bench.py --no-pmc --no-parity-mode > $OUT/bench_headline.json 2>/dev/null; echo "headline rc $?"
-  timeout -k 10 400 python bench.py --no-pmc --no-parity-mode --config shipped > $OUT/bench_shipped.json 2>/dev/null; echo "shipped rc $?"
+  timeout -k 10 400 python bench.py --full --no-pmc --no-parity-mode > $OUT/bench_headline.json 2>/dev/null; echo "headline rc $?"
+  timeout -k 10 400 python bench.py --full --no-pmc --no-parity-mode --config shipped > $OUT/bench_shipped.json 2>/dev/null; echo "shipped rc $?"
 }
 
 s9() {  # pair-wise pinned conversions, DDA exit depths from the voxel index: whole GPU suite, timings, benches
   timeout -k 10 1500 python -m pytest tests -m gpu -q -s -p no:cacheprovider > $OUT/tests.log 2>&1; echo "tests rc $?"; tail -6 $OUT/tests.log
   timeout -k 10 300 python scripts/diag/tunits_check.py > $OUT/tunits_check.log 2>&1; echo "tunits_check rc $?"; grep "f16 split" $OUT/tunits_check.log
   timeout -k 10 600 python scripts/diag/sdf_infer_units.py --pmc > $OUT/sdf_infer_units.log 2>&1; echo "sdf_infer_units rc $?"; cat $OUT/sdf_infer_units.log
-  timeout -k 10 400 python bench.py --no-pmc --no-parity-mode > $OUT/bench_headline.json 2>/dev/null; echo "headline rc $?"
-  timeout -k 10 400 python bench.py --no-pmc --no-parity-mode --config shipped > $OUT/bench_shipped.json 2>/dev/null; echo "shipped rc $?"
+  timeout -k 10 400 python bench.py --full --no-pmc --no-parity-mode > $OUT/bench_headline.json 2>/dev/null; echo "headline rc $?"
+  timeout -k 10 400 python bench.py --full --no-pmc --no-parity-mode --config shipped > $OUT/bench_shipped.json 2>/dev/null; echo "shipped rc $?"
 }
 
 s10() {  # item 3: two blocks per wave with hand-written loads into AGPRs (probe library `asm`); item 5: the timed program's parity under pytest
@@ -95,7 +95,7 @@ s11() {  # one code path for the prefetch segment (no hoisted v_exp burst): prod
 s12() {  # colour activations as pairs in two ring passes instead of three: tests, cost at the shipped shape and at the headline's
   timeout -k 10 900 python -m pytest tests/test_gpu_color_nerf.py tests/test_gpu_fullsize.py tests/test_gpu_render_only.py tests/test_gpu_timed_program_parity.py -q -p no:cacheprovider > $OUT/tests.log 2>&1; echo "tests rc $?"; tail -3 $OUT/tests.log
   for S in 1000 3000; do
-    timeout -k 10 400 python bench.py --no-pmc --no-parity-mode --config shipped --seed $S > $OUT/bench_shipped_seed$S.json 2>/dev/null; echo "shipped seed $S rc $?"
+    timeout -k 10 400 python bench.py --full --no-pmc --no-parity-mode --config shipped --seed $S > $OUT/bench_shipped_seed$S.json 2>/dev/null; echo "shipped seed $S rc $?"
   done
   NEUCONW_COLOR_ASPLIT=1 timeout -k 10 400 $B > $OUT/bench_headline_asplit.json 2>/dev/null; echo "headline + act_split rc $?"
   timeout -k 10 400 $B > $OUT/bench_headline.json 2>/dev/null; echo "headline rc $?"
@@ -118,7 +118,7 @@ s14() {  # W = 512 split kernels: does pinning the weight ring's loads / a deepe
 s15() {  # headline shape, ten ray batches: trained-weights colour and step time with the colour activations as pairs (act_split) and without
   for S in 1000 2000 3000 4000 5000 6000 7000 8000 9000 10000; do
     for A in 0 1; do
-      NEUCONW_COLOR_ASPLIT=$A timeout -k 10 300 python bench.py --no-pmc --no-parity-mode --seed $S > $OUT/bench_seed${S}_asplit$A.json 2>/dev/null; echo "seed $S asplit $A rc $?"
+      NEUCONW_COLOR_ASPLIT=$A timeout -k 10 300 python bench.py --full --no-pmc --no-parity-mode --seed $S > $OUT/bench_seed${S}_asplit$A.json 2>/dev/null; echo "seed $S asplit $A rc $?"
     done
   done
 }
@@ -157,28 +157,28 @@ PY
 
 s19() {  # the shipped shape's trained-weights parity point over ten ray batches (final kernels); the whole GPU suite once more
   for S in 1000 2000 3000 4000 5000 6000 7000 8000 9000 10000; do
-    timeout -k 10 300 python bench.py --no-pmc --no-parity-mode --config shipped --seed $S > $OUT/bench_shipped_seed$S.json 2>/dev/null; echo "shipped seed $S rc $?"
+    timeout -k 10 300 python bench.py --full --no-pmc --no-parity-mode --config shipped --seed $S > $OUT/bench_shipped_seed$S.json 2>/dev/null; echo "shipped seed $S rc $?"
   done
   timeout -k 10 1200 python -m pytest tests -m gpu -q -p no:cacheprovider > $OUT/tests.log 2>&1; echo "tests rc $?"; tail -2 $OUT/tests.log
 }
 
 s20() {  # trained states of the shipped shape's outlier batches for the CPU emulation
   for S in 7000 10000 6000; do
-    timeout -k 10 300 python bench.py --no-pmc --no-parity-mode --config shipped --seed $S --save-trained-state $OUT/trained_shipped_seed$S.pt > $OUT/bench_shipped_seed$S.json 2>/dev/null; echo "shipped seed $S rc $?"
+    timeout -k 10 300 python bench.py --full --no-pmc --no-parity-mode --config shipped --seed $S --save-trained-state $OUT/trained_shipped_seed$S.pt > $OUT/bench_shipped_seed$S.json 2>/dev/null; echo "shipped seed $S rc $?"
   done
 }
 
 s21() {  # phi' of the W = 512 adjoint sweep from h as a hi + lo pair (residual stash): tests, the outlier ray batches, cost
   timeout -k 10 900 python -m pytest tests/test_gpu_sdf.py tests/test_gpu_sdf_train.py tests/test_gpu_fullsize.py tests/test_gpu_render_only.py tests/test_gpu_grid.py -q -s -p no:cacheprovider > $OUT/tests.log 2>&1; echo "tests rc $?"; tail -3 $OUT/tests.log; grep "W=512 normals" $OUT/tests.log
   for S in 7000 1000 5000 10000; do
-    timeout -k 10 300 python bench.py --no-pmc --no-parity-mode --config shipped --seed $S > $OUT/bench_shipped_seed$S.json 2>/dev/null; echo "shipped seed $S rc $?"
+    timeout -k 10 300 python bench.py --full --no-pmc --no-parity-mode --config shipped --seed $S > $OUT/bench_shipped_seed$S.json 2>/dev/null; echo "shipped seed $S rc $?"
   done
 }
 
 s22() {  # whole GPU suite on the residual-stash build; shipped ten ray batches again
   timeout -k 10 1200 python -m pytest tests -m gpu -q -p no:cacheprovider > $OUT/tests.log 2>&1; echo "tests rc $?"; tail -3 $OUT/tests.log
   for S in 2000 3000 4000 6000 8000 9000; do
-    timeout -k 10 300 python bench.py --no-pmc --no-parity-mode --config shipped --seed $S > $OUT/bench_shipped_seed$S.json 2>/dev/null; echo "shipped seed $S rc $?"
+    timeout -k 10 300 python bench.py --full --no-pmc --no-parity-mode --config shipped --seed $S > $OUT/bench_shipped_seed$S.json 2>/dev/null; echo "shipped seed $S rc $?"
   done
 }
 
