@@ -607,6 +607,42 @@ int ncw_mc_emit(const float* sdf, const uint8_t* mask, int Dx, int Dy, int Dz, f
                 const int32_t* ntri, const int32_t* edges, const int64_t* offsets, float* tri_pos, int64_t* tri_key,
                 void* stream);
 
+
+/* ------------------------------------------------------------------------------------------
+ * Exact 1-nearest-neighbour search for the mesh evaluation: replaces the per-point
+ * `scipy.spatial.KDTree.query` loop of utils/eval_utils.py:126-154 (`nn_correspondance`, the use_o3d=False path of
+ * utils/eval_mesh.py:48-123).  Uniform grid of cubic cells over a box chosen by the caller, for the reference cloud
+ * P [M,3] and the queries Q [N,3] (f32, recentred by the caller); points and queries outside the box are clamped into the
+ * boundary cells (exact all the same: boundary faces never bound the search); cell (cx, cy, cz) =
+ * clamp(floor((x - lo) * inv_h), 0, dim - 1), linear key
+ * (cx * dim[1] + cy) * dim[2] + cz.  Distances are Euclidean, d^2 = dx*dx + dy*dy + dz*dz; ties on equal d^2 go to the
+ * smaller index (= argmin of the brute-force distance matrix).  No approximation, no truncation radius.
+ *   ncw_nn_cell_keys  : keys[n] int32 of n points.
+ *   ncw_nn_cell_ranges: after a stable sort of P's keys (sorted_keys[m], order[m] = the permutation): cell_range
+ *                       [dim0*dim1*dim2][2] int32 (ZEROED by the caller) gets [start, end) of every non-empty cell;
+ *                       pts_sorted [m][4] f32 = P in cell order with the original index in .w (int bits).
+ *   ncw_nn_query      : q_order = Q in cell order (stable sort of Q's keys); per query dist[n] f32 / idx[n] int64 at the
+ *                       query's original position, by Chebyshev shells around its cell, stopping after shell r when
+ *                       best d^2 < (b - margin)^2 (b = distance to the faces of the (2r+1)^3 block not on the grid boundary)
+ *                       or when the block covers the grid.  Queries still open after `max_shell` shells are appended to
+ *                       escaped[] (their count in *n_escaped, zeroed by the caller) and left unwritten.
+ *   ncw_nn_brute      : the escaped queries against all of P; scratch uint64[n_esc].
+ * ---------------------------------------------------------------------------------------- */
+typedef struct NcwNnGrid {
+    float lo[3];
+    float h, inv_h;
+    int32_t dim[3];
+} NcwNnGrid;
+
+int ncw_nn_cell_keys(const float* pts, int64_t n, const NcwNnGrid* grid, int32_t* keys, void* stream);
+int ncw_nn_cell_ranges(const float* pts, const int32_t* sorted_keys, const int64_t* order, int64_t m, int32_t* cell_range,
+                       float* pts_sorted, void* stream);
+int ncw_nn_query(const float* pts_sorted, const int32_t* cell_range, const float* q, const int64_t* q_order, int64_t n,
+                 const NcwNnGrid* grid, int max_shell, float margin, float* dist, int64_t* idx, int32_t* escaped,
+                 int32_t* n_escaped, void* stream);
+int ncw_nn_brute(const float* pts_sorted, int64_t m, const float* q, const int32_t* escaped, int64_t n_esc, uint64_t* scratch,
+                 float* dist, int64_t* idx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

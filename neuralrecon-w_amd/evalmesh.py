@@ -1,0 +1,446 @@
+"""Mesh evaluation on the GPU: precision / recall / F-score of a predicted surface against the
+ground-truth point cloud.
+
+Reference: utils/eval_mesh.py:48-123 `eval_mesh` with its use_o3d=False branch (`trimesh_load`, utils/eval_utils.py:61-84)
+and the helpers of utils/eval_utils.py (`_compute` :87-100, `bbx_crop` :103-113, `nn_correspondance` :126-154,
+`filtered_sfm` :157-173, `point_crop` :176-216).  The reference needs kaolin, trimesh and matplotlib to import and answers
+the nearest-neighbour queries with one scipy KDTree query per point; here:
+  * nearest neighbours: exact 1-NN over a uniform grid (csrc/ncw_nn.hip, `nn_distances`) -- same distances, no
+    approximation, ties to the smaller index;
+  * PLY input without trimesh (`read_ply_points`); the ONLY difference from trimesh's vertex array: trimesh merges duplicate
+    vertices when it loads a MESH, and `read_ply_points` removes exact-coordinate duplicates only (our own meshes are already
+    welded, so the step does nothing on them);
+  * the SfM crop with sorted unique cell keys + searchsorted instead of the O(N M) Morton-code compare (`sfm_crop`);
+  * all thresholds from one sort per distance vector (`metrics`).
+File layout and JSON keys are the reference's.
+"""
+import ctypes as C
+import json
+import os
+
+import numpy as np
+import torch
+
+from . import lib as L
+
+F32_EPS = float(np.finfo(np.float32).eps)
+MAX_CELLS = 1 << 24  # cap of the dense cell table (two int32 per cell)
+MAX_SHELL = 8        # Chebyshev shells a query walks before it is handed to the brute-force kernel
+
+
+# ---------------------------------------------------------------------------------------------------
+# exact 1-NN (csrc/ncw_nn.hip)
+# ---------------------------------------------------------------------------------------------------
+def _grid_dims(ext, h):
+    return [max(1, int(np.ceil(e / h))) for e in ext]
+
+
+def _grid_for(ext, target_cells):
+    """Cubic cells of side h over a box of extents `ext` with about `target_cells` cells (at most MAX_CELLS)."""
+    ext = [max(float(e), 0.0) for e in ext]
+    emax = max(ext)
+    if emax <= 0.0:
+        return 1.0, [1, 1, 1]
+    target = max(1, min(int(target_cells), MAX_CELLS))
+    lo_h, hi_h = emax * 1e-7, emax * 1.0001  # hi_h: one cell along the longest edge
+    for _ in range(60):  # geometric bisection: the smallest h whose table fits the target
+        mid = (lo_h * hi_h) ** 0.5
+        n = np.prod(_grid_dims(ext, mid), dtype=np.float64)
+        if n > target:
+            lo_h = mid
+        else:
+            hi_h = mid
+    return hi_h, _grid_dims(ext, hi_h)
+
+
+class NNGrid:
+    """The reference cloud P (f32, recentred) bucketed on a uniform grid.  The grid box is P's own box with its 0.1 % tails on
+    every axis cut off (far outliers would otherwise stretch the cells over the whole scene); points and queries outside it
+    are clamped into the boundary cells.  That keeps the search exact: a point in a cell below the block's lower face lies
+    below that face whether it was clamped or not, and the faces on the grid boundary never enter the stop bound.
+    `coord_max`: the largest |coordinate| of P and the queries (sets the rounding margin of the stop test).  Built once,
+    queried with `query`."""
+
+    def __init__(self, ref32, coord_max, max_shell=MAX_SHELL, target_cells=None):
+        if not ref32.is_cuda:
+            raise L.NeuconwHipError("evalmesh.NNGrid: the reference cloud is not on a GPU; there is no CPU fallback")
+        self.dev = ref32.device
+        self.ref = ref32.contiguous()
+        self.m = int(ref32.shape[0])
+        sample = self.ref[:: max(1, self.m // 65536)]
+        if sample.shape[0] >= 1000:
+            q = torch.quantile(sample, torch.tensor([1e-3, 1 - 1e-3], device=self.dev), dim=0)
+            lo, hi = q[0].tolist(), q[1].tolist()
+        else:
+            lo, hi = self.ref.amin(0).tolist(), self.ref.amax(0).tolist()
+        self.lo = [float(v) for v in lo]
+        self.ext = [float(b) - float(a) for a, b in zip(lo, hi)]
+        self.max_shell = int(max_shell)
+        # rounding of the cell assignment and of the face distances is of order eps * (|x| + extent): the stop test keeps
+        # that much in hand
+        self.margin = 16 * F32_EPS * (float(coord_max) + max(self.ext) + 1e-30)
+        self.refined = False
+        self._build(self.m if target_cells is None else target_cells)
+        if target_cells is None:
+            # surface clouds leave most cells empty and crowd a few: when the fullest cell is far above the mean of the
+            # table, refine once so that the non-empty cells hold about 2 points (area scales as h^-2)
+            counts = self._counts()
+            mean_all = self.m / float(self.ncells)
+            occ = self.m / float(max(1, int((counts > 0).sum())))
+            if int(counts.max()) > 32 * max(mean_all, 1.0) and occ > 4 and self.ncells < MAX_CELLS:
+                self._build(int(min(MAX_CELLS, self.ncells * (occ / 2.0) ** 1.5)))
+                self.refined = True
+
+    def _build(self, target_cells):
+        lib = L.get_lib()
+        h, dims = _grid_for(self.ext, target_cells)
+        self.h, self.dims = h, dims
+        self.ncells = int(dims[0] * dims[1] * dims[2])
+        g = L.NcwNnGrid()
+        for a in range(3):
+            g.lo[a], g.dim[a] = self.lo[a], dims[a]
+        g.h, g.inv_h = h, 1.0 / h
+        self.cgrid = g
+        keys = torch.empty(self.m, dtype=torch.int32, device=self.dev)
+        L.check(lib.ncw_nn_cell_keys(L.ptr(self.ref), self.m, C.byref(g), L.ptr(keys), L.stream_ptr(self.dev)), "ncw_nn_cell_keys")
+        skeys, order = torch.sort(keys, stable=True)
+        self.sorted_keys = skeys.contiguous()
+        self.range = torch.zeros(self.ncells, 2, dtype=torch.int32, device=self.dev)
+        self.pts = torch.empty(self.m, 4, dtype=torch.float32, device=self.dev)
+        L.check(lib.ncw_nn_cell_ranges(L.ptr(self.ref), L.ptr(self.sorted_keys), L.ptr(order.contiguous()), self.m,
+                                       L.ptr(self.range), L.ptr(self.pts), L.stream_ptr(self.dev)), "ncw_nn_cell_ranges")
+
+    def _counts(self):
+        return self.range[:, 1] - self.range[:, 0]
+
+    def query(self, q32, stats=None):
+        """(dist [N] f32, idx [N] int64) of every query's nearest point of P; stats (dict) gets `escaped`."""
+        lib = L.get_lib()
+        n = int(q32.shape[0])
+        q32 = q32.contiguous()
+        dist = torch.empty(n, dtype=torch.float32, device=self.dev)
+        idx = torch.empty(n, dtype=torch.int64, device=self.dev)
+        keys = torch.empty(n, dtype=torch.int32, device=self.dev)
+        s = L.stream_ptr(self.dev)
+        L.check(lib.ncw_nn_cell_keys(L.ptr(q32), n, C.byref(self.cgrid), L.ptr(keys), s), "ncw_nn_cell_keys")
+        q_order = torch.sort(keys, stable=True)[1].contiguous()
+        escaped = torch.empty(n, dtype=torch.int32, device=self.dev)
+        n_esc = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        L.check(lib.ncw_nn_query(L.ptr(self.pts), L.ptr(self.range), L.ptr(q32), L.ptr(q_order), n, C.byref(self.cgrid),
+                                 self.max_shell, float(self.margin), L.ptr(dist), L.ptr(idx), L.ptr(escaped), L.ptr(n_esc), s),
+                "ncw_nn_query")
+        ne = int(n_esc.item())  # one device->host read: the size of the escape launch
+        if ne:
+            scratch = torch.empty(ne, dtype=torch.int64, device=self.dev)
+            L.check(lib.ncw_nn_brute(L.ptr(self.pts), self.m, L.ptr(q32), L.ptr(escaped), ne, L.ptr(scratch), L.ptr(dist),
+                                     L.ptr(idx), s), "ncw_nn_brute")
+        if stats is not None:
+            stats["escaped"] = stats.get("escaped", 0) + ne
+        return dist, idx
+
+
+def recentre(ref, query):
+    """Both clouds moved to their common box centre in float64, then cast to f32 (scene coordinates are metres and may be
+    far from the origin).  Returns (ref32, query32, largest |recentred coordinate|, centre float64 numpy)."""
+    both = [t for t in (ref, query) if t.shape[0] > 0]
+    lo = torch.stack([t.double().amin(0) for t in both]).amin(0).cpu().numpy()
+    hi = torch.stack([t.double().amax(0) for t in both]).amax(0).cpu().numpy()
+    centre = (lo + hi) / 2.0
+    c = torch.from_numpy(centre).to(ref.device)
+    r32 = (ref.double() - c).float().contiguous()
+    q32 = (query.double() - c).float().contiguous()
+    cmax = float(torch.maximum(r32.abs().amax(), q32.abs().amax()))
+    return r32, q32, cmax, centre
+
+
+@torch.no_grad()
+def nn_distances(ref, query, max_shell=MAX_SHELL, stats=None):
+    """For every query point its Euclidean distance to the nearest point of `ref` and that point's index -- exact, ties to the
+    smaller index (utils/eval_utils.py:126-154 `nn_correspondance(ref, query)`).  ref [M,3], query [N,3]: GPU tensors (any
+    float dtype).  Returns (dist [N] float32, idx [N] int64); empty results when either side is empty (as the reference).
+    stats (dict, optional) gets the grid shape and the number of queries that took the brute-force path (`escaped`)."""
+    if not (ref.is_cuda and query.is_cuda):
+        raise L.NeuconwHipError("evalmesh.nn_distances: the clouds are not on a GPU; there is no CPU fallback")
+    dev = ref.device
+    ref, query = ref.reshape(-1, 3), query.reshape(-1, 3)
+    if ref.shape[0] == 0 or query.shape[0] == 0:
+        return torch.zeros(0, dtype=torch.float32, device=dev), torch.zeros(0, dtype=torch.int64, device=dev)
+    r32, q32, cmax, _ = recentre(ref, query)
+    grid = NNGrid(r32, cmax, max_shell=max_shell)
+    if stats is not None:
+        stats.update(dims=list(grid.dims), cells=grid.ncells, refined=grid.refined)
+    return grid.query(q32, stats)
+
+
+# ---------------------------------------------------------------------------------------------------
+# PLY / COLMAP input
+# ---------------------------------------------------------------------------------------------------
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
+              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
+              "double": "f8", "float64": "f8"}
+
+
+def _ply_header(fh):
+    if fh.readline().strip() != b"ply":
+        raise ValueError("not a PLY file")
+    fmt, elements = None, []
+    while True:
+        line = fh.readline()
+        if not line:
+            raise ValueError("PLY header without end_header")
+        tok = line.decode("ascii", "replace").split()
+        if not tok or tok[0] in ("comment", "obj_info"):
+            continue
+        if tok[0] == "format":
+            fmt = tok[1]
+        elif tok[0] == "element":
+            elements.append({"name": tok[1], "count": int(tok[2]), "props": []})
+        elif tok[0] == "property":
+            if tok[1] == "list":
+                elements[-1]["props"].append((tok[4], "list", _PLY_TYPES[tok[2]], _PLY_TYPES[tok[3]]))
+            else:
+                elements[-1]["props"].append((tok[2], _PLY_TYPES[tok[1]], None, None))
+        elif tok[0] == "end_header":
+            return fmt, elements
+
+
+def read_ply_points(path, weld=None):
+    """float64 [V,3] vertex coordinates (x, y, z) of an ascii / binary_little_endian / binary_big_endian PLY with any vertex
+    property list; other elements (faces, ...) are skipped.  What trimesh.load(...).vertices gives (utils/eval_utils.py:65,71),
+    except for one thing: trimesh merges duplicate vertices when it loads a MESH -- here a file with faces (weld=None) or
+    weld=True drops exact-coordinate duplicates, first occurrence kept, order preserved.  mesh.write_ply's files are welded
+    already, so this changes nothing on them."""
+    with open(path, "rb") as fh:
+        fmt, elements = _ply_header(fh)
+        body = fh.read()
+    n_faces = sum(e["count"] for e in elements if e["name"] == "face")
+    verts = None
+    if fmt == "ascii":
+        lines = body.decode("ascii").splitlines()
+        row = 0
+        for e in elements:
+            if e["name"] == "vertex":
+                names = [p[0] for p in e["props"]]
+                if any(p[1] == "list" for p in e["props"]):
+                    raise ValueError("list property in the vertex element")
+                cols = [names.index(c) for c in ("x", "y", "z")]
+                data = np.array([lines[row + i].split() for i in range(e["count"])], dtype=np.float64).reshape(-1, len(names))
+                verts = data[:, cols]
+                break
+            row += e["count"]
+    elif fmt in ("binary_little_endian", "binary_big_endian"):
+        bo = "<" if fmt == "binary_little_endian" else ">"
+        off = 0
+        for e in elements:
+            if any(p[1] == "list" for p in e["props"]):
+                if e["name"] == "vertex":
+                    raise ValueError("list property in the vertex element")
+                for _ in range(e["count"]):  # variable-length rows: walk them
+                    for _, kind, ct, it in e["props"]:
+                        if kind == "list":
+                            cnt = int(np.frombuffer(body, bo + ct, 1, off)[0])
+                            off += np.dtype(ct).itemsize + cnt * np.dtype(it).itemsize
+                        else:
+                            off += np.dtype(kind).itemsize
+                continue
+            dt = np.dtype([(p[0], bo + p[1]) for p in e["props"]])
+            if e["name"] == "vertex":
+                rec = np.frombuffer(body, dt, e["count"], off)
+                verts = np.stack([rec[c].astype(np.float64) for c in ("x", "y", "z")], -1)
+                break
+            off += dt.itemsize * e["count"]
+    else:
+        raise ValueError("unknown PLY format %r" % fmt)
+    if verts is None:
+        verts = np.zeros((0, 3), dtype=np.float64)
+    verts = np.ascontiguousarray(verts, dtype=np.float64).reshape(-1, 3)
+    if (n_faces > 0 if weld is None else weld) and verts.shape[0]:
+        _, first = np.unique(verts, axis=0, return_index=True)
+        verts = verts[np.sort(first)]
+    return verts
+
+
+def apply_transform(points, T):
+    """(T[:3] @ [p, 1]^T)^T in float64: the reference's homogeneous product (eval_utils.py:70-71, :167-168)."""
+    T = np.asarray(T, dtype=np.float64)
+    p = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    ph = np.concatenate((p, np.ones((p.shape[0], 1))), axis=-1)
+    return (T[:3] @ ph.T).T
+
+
+def read_points3d_filtered(path, track_length, reproj_error, sfm_to_gt=None):
+    """utils/eval_utils.py:157-173 `filtered_sfm`: COLMAP points with a track STRICTLY longer than `track_length` and a mean
+    reprojection error STRICTLY below `reproj_error`, carried to GT coordinates by `sfm_to_gt` (4x4; None = identity).
+    `path`: points3D.bin or the directory holding it.  float64 [K,3] ([0,3] when none passes; the reference raises there)."""
+    from . import voxel
+
+    if os.path.isdir(path):
+        path = os.path.join(path, "points3D.bin")
+    xyz, err, track = voxel.read_points3d(path)
+    keep = (track > track_length) & (err < reproj_error)
+    pts = xyz[keep]
+    return pts if sfm_to_gt is None else apply_transform(pts, sfm_to_gt)
+
+
+# ---------------------------------------------------------------------------------------------------
+# crops and metrics
+# ---------------------------------------------------------------------------------------------------
+def bbx_crop(points, bbx):
+    """utils/eval_utils.py:103-113: the points strictly inside the box (normalised coordinates in the open (-1, 1)^3)."""
+    points = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    bmin, bmax = np.array(bbx[0], dtype=np.float64), np.array(bbx[1], dtype=np.float64)
+    origin = bmin + (bmax - bmin) / 2
+    scale = (bmax - bmin) / 2
+    pn = (points - origin) / scale
+    return points[(pn > -1).all(-1) & (pn < 1).all(-1)]
+
+
+def sfm_crop(points, sfm_points, voxel_size, bbx):
+    """utils/eval_utils.py:176-216 `point_crop`: keep the points whose voxel holds an SfM point.  Cube of half-size
+    (longest box edge) / 2 around the box centre, res = floor(2 scale / voxel_size), cell = floor(res (x + 1) / 2) per axis
+    with NO clamp.  The reference compares every point's kaolin Morton code against every SfM code (O(N M)); here sorted
+    unique cell keys + searchsorted.  One difference: SfM cells outside [0, res)^3 are dropped.  In the reference such a cell
+    could only match through kaolin's Morton code of negative / overflowing int16 coordinates, which cannot be pinned
+    without kaolin; points outside the cube therefore never survive the crop here."""
+    points = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    sfm_points = np.asarray(sfm_points, dtype=np.float64).reshape(-1, 3)
+    bmin, bmax = np.array(bbx[0], dtype=np.float64), np.array(bbx[1], dtype=np.float64)
+    dim = np.max(bmax - bmin)
+    origin = bmin + (bmax - bmin) / 2
+    scale = dim / 2
+    res = int(np.floor(2 * scale / voxel_size))
+
+    def cells(p):
+        q = np.floor(res * ((p - origin) / scale + 1.0) / 2.0)
+        ok = ((q >= 0) & (q < res)).all(-1)
+        qi = np.where(ok[:, None], q, 0).astype(np.int64)
+        return (qi[:, 0] * res + qi[:, 1]) * res + qi[:, 2], ok
+
+    if points.shape[0] == 0 or sfm_points.shape[0] == 0:
+        return points[:0]
+    sk, sok = cells(sfm_points)
+    sk = np.unique(sk[sok])
+    pk, pok = cells(points)
+    if sk.shape[0] == 0:
+        return points[:0]
+    pos = np.clip(np.searchsorted(sk, pk), 0, sk.shape[0] - 1)
+    return points[pok & (sk[pos] == pk)]
+
+
+def _as_f64(d, dev=None):
+    if torch.is_tensor(d):
+        return d.reshape(-1).double()
+    return torch.as_tensor(np.asarray(d, dtype=np.float64).reshape(-1), device=dev)
+
+
+@torch.no_grad()
+def metrics(d_gt_to_pred, d_pred_to_gt, thresholds):
+    """utils/eval_utils.py:87-100 `_compute` for every threshold (list of dicts, the reference's keys): `dist1` = mean
+    pred->gt distance, `dist2` = mean gt->pred distance, `prec` = fraction of pred->gt distances < t, `recal` = fraction of
+    gt->pred distances < t (both floored at 1e-6), `fscore` = 2 prec recal / (prec + recal).  Each distance vector is sorted
+    once (float64, on its device) and counted with searchsorted.  Empty vectors give NaN, as numpy's mean does."""
+    single = not isinstance(thresholds, (list, tuple, np.ndarray))
+    ts = [float(thresholds)] if single else [float(t) for t in thresholds]
+    dev = d_gt_to_pred.device if torch.is_tensor(d_gt_to_pred) else None
+    a = _as_f64(d_gt_to_pred, dev)    # reference dist1
+    b = _as_f64(d_pred_to_gt, a.device)  # reference dist2
+    t = torch.tensor(ts, dtype=torch.float64, device=a.device)
+
+    def frac_below(d):
+        if d.numel() == 0:
+            return [float("nan")] * len(ts)
+        cnt = torch.searchsorted(torch.sort(d)[0], t, right=False)  # number of entries strictly below t
+        n = d.numel()
+        return [c / n for c in cnt.cpu().tolist()]  # correctly rounded on the host, as numpy's mean of the 0/1 vector
+
+    def mean(d):
+        return float(d.mean()) if d.numel() else float("nan")
+
+    pa, pb = frac_below(a), frac_below(b)
+    m1, m2 = mean(b), mean(a)
+    out = []
+    for i in range(len(ts)):
+        precision = max(pb[i], 1e-6)  # Python's max keeps a NaN first argument, like the reference
+        recal = max(pa[i], 1e-6)
+        fscore = 2 * precision * recal / (precision + recal)
+        out.append({"dist1": m1, "dist2": m2, "prec": precision, "recal": recal, "fscore": fscore})
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------
+# the evaluation (utils/eval_mesh.py:48-123, use_o3d=False)
+# ---------------------------------------------------------------------------------------------------
+def _write_points(path, pts):
+    from . import mesh
+
+    v = torch.from_numpy(np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3))
+    mesh.write_ply(path, v, torch.zeros(0, 3, dtype=torch.int64))
+
+
+def eval_mesh(file_pred, file_trgt, scene_config, is_mesh, threshold=.1, bbx_name="eval_bbx", save_name="eval", sfm=None,
+              device=None, verbose=True):
+    """utils/eval_mesh.py:48-123 with use_o3d=False: load both PLYs (read_ply_points; `is_mesh` is accepted and, as in the
+    reference's trimesh branch, not used), carry the prediction to GT coordinates by scene_config['sfm2gt'], crop both to
+    scene_config[bbx_name], optionally crop both to the voxels of the filtered SfM points, nearest neighbours in both
+    directions on the GPU, metrics per threshold.  `sfm`: dict(path, track_length, reproj_error, voxel_size), or the
+    reference's scene_config keys sfm_path / eval_tl / eval_error / eval_voxel.  Writes under
+    <dir of file_pred>/eval_<save_name>/: down_gt.ply, down_pred_in_gt.ply, [sfm_points.ply, pred_filtered.ply,
+    target_filtered.ply], visualize/<t:.2f>/metrics.json and metrics.json (thresholds, fscores, precs, recals).  Returns the
+    last threshold's metrics dict."""
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    save_dir = os.path.join(os.path.dirname(file_pred), "eval_" + str(save_name))
+    os.makedirs(save_dir, exist_ok=True)
+    log = print if verbose else (lambda *a, **k: None)
+    log("results will save in %s" % save_dir)
+    sfm_to_gt = np.array(scene_config["sfm2gt"], dtype=np.float64)
+
+    verts_trgt = bbx_crop(read_ply_points(file_trgt), scene_config[bbx_name])
+    _write_points(os.path.join(save_dir, "down_gt.ply"), verts_trgt)
+    verts_pred = bbx_crop(apply_transform(read_ply_points(file_pred), sfm_to_gt), scene_config[bbx_name])
+    _write_points(os.path.join(save_dir, "down_pred_in_gt.ply"), verts_pred)
+
+    if sfm is None and "sfm_path" in scene_config:
+        sfm = {"path": scene_config["sfm_path"], "track_length": scene_config["eval_tl"],
+               "reproj_error": scene_config["eval_error"], "voxel_size": scene_config["eval_voxel"]}
+    if sfm is not None:
+        sfm_pts = read_points3d_filtered(sfm["path"], sfm["track_length"], sfm["reproj_error"], sfm_to_gt)
+        _write_points(os.path.join(save_dir, "sfm_points.ply"), sfm_pts)
+        log("filtered points: %d" % sfm_pts.shape[0])
+        verts_pred = sfm_crop(verts_pred, sfm_pts, sfm["voxel_size"], scene_config[bbx_name])
+        _write_points(os.path.join(save_dir, "pred_filtered.ply"), verts_pred)
+        verts_trgt = sfm_crop(verts_trgt, sfm_pts, sfm["voxel_size"], scene_config[bbx_name])
+        _write_points(os.path.join(save_dir, "target_filtered.ply"), verts_trgt)
+
+    p = torch.from_numpy(verts_pred).to(dev)
+    g = torch.from_numpy(verts_trgt).to(dev)
+    dist1, _ = nn_distances(p, g)  # for every GT point its nearest prediction (eval_mesh.py:88)
+    dist2, _ = nn_distances(g, p)  # for every predicted point its nearest GT point (:89)
+
+    thresholds = list(threshold) if isinstance(threshold, (list, tuple, np.ndarray)) else [threshold]
+    all_m = metrics(dist1, dist2, thresholds)
+    fscores, precs, recals = [], [], []
+    for t, m in zip(thresholds, all_m):
+        save_path = os.path.join(save_dir, "visualize", "%.2f" % t)
+        os.makedirs(save_path, exist_ok=True)
+        with open(os.path.join(save_path, "metrics.json"), "w") as fh:
+            json.dump(m, fh)
+        fscores.append(m["fscore"])
+        precs.append(m["prec"])
+        recals.append(m["recal"])
+    with open(os.path.join(save_dir, "metrics.json"), "w") as fh:
+        json.dump({"thresholds": [float(t) for t in thresholds], "fscores": fscores, "precs": precs, "recals": recals}, fh)
+    log("fscores: %s" % fscores)
+    log("precs: %s" % precs)
+    log("recals: %s" % recals)
+    return all_m[-1]
+
+
+def parse_thresholds(text):
+    """utils/eval_mesh.py:127-129: "start,end,interval" -> list(np.arange(start, end, interval)); a single value "0.1" ->
+    [0.1]."""
+    vals = [float(v.strip()) for v in str(text).split(",") if v.strip()]
+    if len(vals) == 1:
+        return vals
+    if len(vals) != 3:
+        raise ValueError("--threshold takes one value or start,end,interval (got %r)" % text)
+    return [float(v) for v in np.arange(vals[0], vals[1], vals[2])]

@@ -11,7 +11,10 @@
   * cos_anneal_ratio = min(1, step / ANNEAL_END); every UPDATE_FREQ steps the fine octree is rebuilt from the current SDF
     (coarse octree from the COLMAP points: voxel.octree_from_sfm); checkpoints every SAVE_FREQ steps in the reference's
     PyTorch-Lightning layout (state_dict keys + torch.optim.Adam optimizer state), readable by its load_ckpt;
-  * LR_SCHEDULER none / cosine / steplr stepped per epoch like PL steps the reference's scheduler (config.lr_at_epoch).
+  * LR_SCHEDULER none / cosine / steplr stepped per epoch like PL steps the reference's scheduler (config.lr_at_epoch);
+  * --val_mesh_every N (opt-in): every N steps the meshes of the reference's validation_step (neuconw_system.py:466-530) --
+    128^3 over the unit sphere and 256^3 over `eval_bbx_detail` -- go to <SAVE_DIR>/<exp_name>/meshes/, and when
+    <root_dir>/gt.ply exists rank 0 scores the detailed one at 0.1 (neuralrecon_w_amd.evalmesh).
 """
 import argparse
 import os
@@ -27,6 +30,44 @@ from neuralrecon_w_amd import config as C  # noqa: E402
 from neuralrecon_w_amd import raycache, trainer, voxel  # noqa: E402
 
 
+def validation_meshes(rdr, scene, root, save_dir, step, rank, log_detail_skip=True):
+    """neuconw_system.py:466-530: the 128^3 mesh over the unit sphere and the 256^3 mesh over the scene's eval_bbx_detail
+    (carried into SfM space by inv(sfm2gt)), extracted on EVERY rank (the grid sweep is collective); rank 0 writes
+    meshes/<step:08d>.ply and <step:08d>_detail.ply and, when <root>/gt.ply exists, scores the detailed mesh at 0.1
+    (evalmesh.eval_mesh, is_mesh=False, bbx_name=eval_bbx_detail).  Returns the metrics dict or None."""
+    import numpy as np
+
+    from neuralrecon_w_amd import evalmesh, mesh
+
+    mesh_dir = os.path.join(save_dir, "meshes")
+    m = mesh.extract_mesh(rdr, 128, scene["radius"], scene["origin"], with_color=False)
+    if rank == 0:
+        os.makedirs(mesh_dir, exist_ok=True)
+        mesh.write_ply(os.path.join(mesh_dir, "%08d.ply" % step), m["vertices"], m["faces"])
+    if "eval_bbx_detail" not in scene:
+        if rank == 0 and log_detail_skip:
+            print("[val] step %d: the scene config has no eval_bbx_detail: detail mesh and evaluation skipped" % step)
+        return None
+    gt_to_sfm = np.linalg.inv(np.array(scene["sfm2gt"], dtype=np.float64))
+    v1 = gt_to_sfm[:3, :3] @ np.array(scene["eval_bbx_detail"][0], dtype=np.float64) + gt_to_sfm[:3, 3]
+    v2 = gt_to_sfm[:3, :3] @ np.array(scene["eval_bbx_detail"][1], dtype=np.float64) + gt_to_sfm[:3, 3]
+    bmin, bmax = np.minimum(v1, v2), np.maximum(v1, v2)
+    centre, half = (bmax + bmin) / 2, np.max(bmax - bmin) / 2
+    so, radius = np.asarray(scene["origin"], dtype=np.float64), float(scene["radius"])
+    md = mesh.extract_mesh(rdr, 256, radius, scene["origin"], origin=((centre - so) / radius).tolist(), radius=half / radius,
+                           with_color=False)
+    if rank != 0:
+        return None
+    detail = os.path.join(mesh_dir, "%08d_detail.ply" % step)
+    mesh.write_ply(detail, md["vertices"], md["faces"])
+    gt_path = os.path.join(root, "gt.ply")
+    if not os.path.exists(gt_path):
+        return None
+    met = evalmesh.eval_mesh(detail, gt_path, scene, is_mesh=False, threshold=0.1, bbx_name="eval_bbx_detail", verbose=False)
+    print("[val] step %d: prec %.6f recal %.6f fscore %.6f" % (step, met["prec"], met["recal"], met["fscore"]))
+    return met
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cfg_path", required=True)
@@ -39,6 +80,9 @@ def main():
                     help="training precision; default = the package default (NEUCONW_PREC, f16: neuconw.default_prec)")
     ap.add_argument("--ckpt_path", default="", help="resume from this checkpoint")
     ap.add_argument("--log_every", type=int, default=100)
+    ap.add_argument("--val_mesh_every", type=int, default=0,
+                    help="every N steps: validation meshes (128^3 + 256^3 eval_bbx_detail) and, with <root_dir>/gt.ply, "
+                         "their F-score at 0.1 (0 = off)")
     args = ap.parse_args()
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -125,6 +169,7 @@ def main():
     # bound before the loop: a checkpoint whose epoch is already >= --num_epochs (or a loop whose body never runs) still
     # writes last.ckpt below
     epoch, in_epoch, gen_state0 = first_epoch, skip, gen.get_state()
+    val_logged = False  # the "no eval_bbx_detail" line is printed once
     for epoch in range(first_epoch, args.num_epochs):
         if hasattr(step_fn.opt, "lr"):  # utils/__init__.py:45-61: the scheduler steps once per epoch
             step_fn.opt.lr = C.lr_at_epoch(cfg, lr, epoch, args.num_epochs)
@@ -152,6 +197,9 @@ def main():
                          "%d skipped so far)" % (rdr.grad_scale, step_fn.opt.skipped_steps)))
                 t_last = now
             step += 1
+            if args.val_mesh_every > 0 and step % args.val_mesh_every == 0:  # neuconw_system.py:466-530
+                validation_meshes(rdr, scene, root, save_dir, step, rank, log_detail_skip=not val_logged)
+                val_logged = True
             if args.max_steps and step >= args.max_steps:
                 done = True
                 break
