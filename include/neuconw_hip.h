@@ -643,6 +643,46 @@ int ncw_nn_query(const float* pts_sorted, const int32_t* cell_range, const float
 int ncw_nn_brute(const float* pts_sorted, int64_t m, const float* q, const int32_t* escaped, int64_t n_esc, uint64_t* scratch,
                  float* dist, int64_t* idx, void* stream);
 
+
+/* ------------------------------------------------------------------------------------------
+ * Triangle depth rasterizer of the reprojection visibility filter: replaces the pyrender depth render of
+ * utils/pyrender_renderer.py:16-24 (utils/reproj_filter.py:208), the back-projection `reproject` of
+ * utils/reproj_filter.py:133-152 and the per-pixel open3d KD-tree marking loop of :229-232 (with ncw_nn_*).
+ * One view: camera = view[:, :3] v + view[:, 3] (row-major 3x4, OpenCV axes: x right, y down, looking along +z); pixel
+ * (r, c) samples the image point (c + 0.5, r + 0.5) of u = fx x / z + cx, v = fy y / z + cy; linear depth z.  Faces with
+ * every vertex in front of znear or beyond zfar are dropped, faces crossing znear are clipped to it (OpenGL's clip), samples
+ * beyond zfar are dropped.  cull = 1 drops back faces (signed area > 0 in pixel coordinates), 0 draws both sides; zero-area
+ * triangles are dropped.  A sample is covered when all three edge functions are >= 0 (antisymmetric on shared edges: no
+ * holes).  Depth is perspective-correct; the z-buffer zbuf[height * width] uint64 (filled with 0xff.. by the caller) is a
+ * 64-bit atomicMin of (float bits of z << 32 | face): nearest first, equal depth to the smaller face, order-independent.
+ *   ncw_raster_small      : every face; sub-triangles whose pixel box holds at most small_max samples are rasterized by
+ *                           their lane, the others appended as (2 face + sub) to large[] (capacity 2 n_faces, count in
+ *                           *n_large, zeroed by the caller).  n_faces < 2^30.
+ *   ncw_raster_large      : the large list (min(*n_large, max_large) entries), one workgroup per entry.
+ *   ncw_raster_resolve    : depth[n_pix] f32 (0 = empty), face[n_pix] int32 (-1 = empty; NULL = not written).
+ *   ncw_raster_backproject: for the n listed pixels pix[] (linear r * width + c), pts[n][3] = M[:, :3] (c d, r d, d) + M[:, 3]
+ *                           with d = depth[pix] and M row-major 3x4 on the host (pose K^-1 | pose translation): the
+ *                           reference's INTEGER pixel coordinates.
+ *   ncw_raster_mark       : flags[idx[i]] = 1 (uint8[m]) for every i < n with dist[i] < thr.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct NcwRasterView {
+    float view[12];
+    float fx, fy, cx, cy;
+    float znear, zfar;
+    int32_t height, width;
+    int32_t cull;
+    int32_t small_max;
+} NcwRasterView;
+
+int ncw_raster_small(const float* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const NcwRasterView* view,
+                     uint64_t* zbuf, int32_t* large, int32_t* n_large, void* stream);
+int ncw_raster_large(const float* verts, int64_t n_verts, const int32_t* faces, const NcwRasterView* view, const int32_t* large,
+                     const int32_t* n_large, int64_t max_large, uint64_t* zbuf, void* stream);
+int ncw_raster_resolve(const uint64_t* zbuf, int64_t n_pix, float* depth, int32_t* face, void* stream);
+int ncw_raster_backproject(const float* depth, const int64_t* pix, int64_t n, int32_t width, const float* M, float* pts,
+                           void* stream);
+int ncw_raster_mark(const float* dist, const int64_t* idx, int64_t n, float thr, int64_t m, uint8_t* flags, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,475 @@
+"""Reprojection visibility filter on the GPU: the first step of the reference's evaluation pipeline
+(scripts/eval_pipeline.sh), which keeps only the mesh vertices some training camera sees before the F-score is taken.
+
+Reference: utils/reproj_filter.py (`get_train_ids` :70-83, `sfm2gt` :85-92, `load_mesh_to_render` :101-130, `reproject`
+:133-152, `reprojection_worker` :172-243, `__main__` :254-300), utils/pyrender_renderer.py and tools/reproj_error.py:68-91
+(`get_entrinsics`, `get_intrinsic`).  The reference renders every training view with pyrender (OpenGL / EGL), back-projects
+every valid pixel and runs one open3d KD-tree query per pixel in a Python loop; here:
+  * depth: the triangle rasterizer of csrc/ncw_raster.hip (`render_depth`), pyrender's conventions;
+  * back-projection and marking: ncw_raster_backproject / ncw_raster_mark, nearest neighbours by evalmesh.NNGrid (exact,
+    ties to the smaller index);
+  * COLMAP cameras.bin / images.bin and the tsv split read here (no pandas, no open3d, no trimesh); PINHOLE cameras only;
+  * one process, one GPU: the views are independent and run one after another.
+"""
+import csv
+import ctypes as C
+import glob
+import os
+import struct
+
+import numpy as np
+import torch
+import yaml
+
+from . import evalmesh
+from . import lib as L
+
+ZNEAR, ZFAR = 0.05, 100.0  # pyrender.IntrinsicsCamera's defaults (in the units of the rendered frame)
+SMALL_MAX = 32  # sub-triangles whose pixel box holds more samples go to the workgroup-per-triangle kernel
+CULL = {"back": 1, "none": 0}
+
+# COLMAP camera models: id -> (name, number of parameters)
+CAMERA_MODELS = {0: ("SIMPLE_PINHOLE", 3), 1: ("PINHOLE", 4), 2: ("SIMPLE_RADIAL", 4), 3: ("RADIAL", 5), 4: ("OPENCV", 8),
+                 5: ("OPENCV_FISHEYE", 8), 6: ("FULL_OPENCV", 12), 7: ("FOV", 5), 8: ("SIMPLE_RADIAL_FISHEYE", 4),
+                 9: ("RADIAL_FISHEYE", 5), 10: ("THIN_PRISM_FISHEYE", 12)}
+PINHOLE = 1
+# what pandas.read_csv reads as a missing value (its default na_values): such an `id` is null
+_NA = {"", "#N/A", "#N/A N/A", "#NA", "-1.#IND", "-1.#QNAN", "-NaN", "-nan", "1.#IND", "1.#QNAN", "<NA>", "N/A", "NA", "NULL",
+       "NaN", "None", "n/a", "nan", "null"}
+
+
+# ---------------------------------------------------------------------------------------------------
+# COLMAP model and the train split
+# ---------------------------------------------------------------------------------------------------
+def read_cameras_binary(path):
+    """COLMAP cameras.bin: {camera_id: dict(id, model, width, height, params float64)}.  Layout (little-endian): uint64
+    count, then per camera int32 id, int32 model id, uint64 width, uint64 height, float64 params[n(model)].  Only PINHOLE
+    cameras (fx, fy, cx, cy) are accepted: any other model is refused with a ValueError (the reference would read the
+    first four parameters of any model as fx, fy, cx, cy)."""
+    cams = {}
+    with open(path, "rb") as fh:
+        (n,) = struct.unpack("<Q", fh.read(8))
+        for _ in range(n):
+            cid, model, width, height = struct.unpack("<iiQQ", fh.read(24))
+            if model != PINHOLE:
+                name = CAMERA_MODELS.get(model, ("unknown model id %d" % model,))[0]
+                raise ValueError("%s: camera %d is %s; only PINHOLE cameras (undistorted images) are supported" % (path, cid, name))
+            params = np.frombuffer(fh.read(8 * 4), dtype="<f8").astype(np.float64)
+            cams[cid] = {"id": cid, "model": model, "width": int(width), "height": int(height), "params": params}
+    return cams
+
+
+def read_images_binary(path):
+    """COLMAP images.bin: {image_id: dict(id, qvec, tvec, camera_id, name)} (the 2-D points are skipped).  Layout: uint64
+    count, then per image int32 id, float64 qvec[4] (w, x, y, z), float64 tvec[3], int32 camera id, the name as
+    NUL-terminated bytes, uint64 n2d, n2d x (float64 x, float64 y, int64 point3D id)."""
+    imgs = {}
+    with open(path, "rb") as fh:
+        (n,) = struct.unpack("<Q", fh.read(8))
+        for _ in range(n):
+            rec = struct.unpack("<i7di", fh.read(64))
+            name = bytearray()
+            while True:
+                ch = fh.read(1)
+                if ch in (b"\x00", b""):
+                    break
+                name += ch
+            (n2d,) = struct.unpack("<Q", fh.read(8))
+            fh.seek(24 * n2d, os.SEEK_CUR)
+            imgs[rec[0]] = {"id": rec[0], "qvec": np.array(rec[1:5]), "tvec": np.array(rec[5:8]), "camera_id": rec[8],
+                            "name": name.decode("utf-8")}
+    return imgs
+
+
+def qvec2rotmat(q):
+    """Rotation of the unit quaternion (w, x, y, z) (COLMAP's convention: world -> camera)."""
+    w, x, y, z = [float(v) for v in q]
+    return np.array([[1 - 2 * y * y - 2 * z * z, 2 * x * y - 2 * w * z, 2 * z * x + 2 * w * y],
+                     [2 * x * y + 2 * w * z, 1 - 2 * x * x - 2 * z * z, 2 * y * z - 2 * w * x],
+                     [2 * z * x - 2 * w * y, 2 * y * z + 2 * w * x, 1 - 2 * x * x - 2 * y * y]])
+
+
+def read_train_split(data_path, images):
+    """utils/reproj_filter.py:70-83 `get_train_ids`: the rows of the first <data_path>/*.tsv (sorted by name) with a non-null
+    `id` and split == 'train', in file order, as COLMAP image ids (through the image names).  A filename of a row with an
+    id that is not in images.bin is an error, as in the reference."""
+    tsvs = sorted(glob.glob(os.path.join(data_path, "*.tsv")))
+    if not tsvs:
+        raise FileNotFoundError("no *.tsv split file in %s" % data_path)
+    by_name = {im["name"]: iid for iid, im in images.items()}
+    ids = []
+    with open(tsvs[0], newline="") as fh:
+        for row in csv.DictReader(fh, delimiter="\t"):
+            if (row.get("id") or "").strip() in _NA:
+                continue
+            name = row["filename"]
+            if name not in by_name:
+                raise KeyError("%s: image %r is not in images.bin" % (tsvs[0], name))
+            if row.get("split") == "train":
+                ids.append(by_name[name])
+    return ids
+
+
+def load_views(data_path, sfm2gt=None):
+    """The training views of <data_path>: list of dict(id, name, E 4x4 world -> camera (SfM frame, float64), K 3x3 (float32
+    values, as tools/reproj_error.py:84-88 builds it), wh (width, height), E_gt = E inv(sfm2gt) (utils/reproj_filter.py:175),
+    pose = inv(E_gt))."""
+    sp = os.path.join(data_path, "dense", "sparse")
+    images = read_images_binary(os.path.join(sp, "images.bin"))
+    cams = read_cameras_binary(os.path.join(sp, "cameras.bin"))
+    S = np.eye(4) if sfm2gt is None else np.asarray(sfm2gt, dtype=np.float64)
+    S_inv = np.linalg.inv(S)
+    views = []
+    for iid in read_train_split(data_path, images):
+        im = images[iid]
+        cam = cams[im["camera_id"]]
+        E = np.eye(4)
+        E[:3, :3] = qvec2rotmat(im["qvec"])
+        E[:3, 3] = im["tvec"]
+        p = cam["params"]
+        K = np.array([[p[0], 0, p[2]], [0, p[1], p[3]], [0, 0, 1]], dtype=np.float32)
+        E_gt = E @ S_inv
+        views.append({"id": iid, "name": im["name"], "E": E, "K": K, "wh": (cam["width"], cam["height"]), "E_gt": E_gt,
+                      "pose": np.linalg.inv(E_gt)})
+    return views
+
+
+def read_sfm2gt(data_path):
+    with open(os.path.join(data_path, "config.yaml")) as fh:
+        return np.array(yaml.safe_load(fh)["sfm2gt"], dtype=np.float64)
+
+
+# ---------------------------------------------------------------------------------------------------
+# PLY
+# ---------------------------------------------------------------------------------------------------
+def read_ply_mesh(path):
+    """(vertices float64 [V,3], faces int64 [F,3], colours uint8 [V,3] or None) of an ascii / binary PLY, vertices as stored
+    (no welding: trimesh.load(process=False) and open3d.io.read_point_cloud read them so).  Colours: the vertex properties
+    red / green / blue (uchar; other integer types are cast).  Faces: the `vertex_indices` / `vertex_index` list of the face
+    element; polygons with more than three corners are fanned (0, i, i + 1) as trimesh does."""
+    with open(path, "rb") as fh:
+        fmt, elements = evalmesh._ply_header(fh)
+        body = fh.read()
+    verts = np.zeros((0, 3))
+    cols, faces = None, np.zeros((0, 3), dtype=np.int64)
+
+    def vertex_arrays(get):
+        v = np.stack([get(c).astype(np.float64) for c in ("x", "y", "z")], -1).reshape(-1, 3)
+        names = get(None)
+        c = None
+        if all(k in names for k in ("red", "green", "blue")):
+            c = np.stack([get(k) for k in ("red", "green", "blue")], -1).astype(np.uint8).reshape(-1, 3)
+        return v, c
+
+    def fan(polys):
+        tri = [np.stack([p[0].repeat(len(p) - 2), p[1:-1], p[2:]], -1) for p in polys if len(p) >= 3]
+        return np.concatenate(tri).astype(np.int64) if tri else np.zeros((0, 3), dtype=np.int64)
+
+    if fmt == "ascii":
+        lines = body.decode("ascii").splitlines()
+        row = 0
+        for e in elements:
+            rows = [lines[row + i].split() for i in range(e["count"])]
+            row += e["count"]
+            if e["name"] == "vertex":
+                names = [p[0] for p in e["props"]]
+                data = np.array(rows, dtype=np.float64).reshape(-1, len(names))
+                verts, cols = vertex_arrays(lambda k: names if k is None else data[:, names.index(k)])
+            elif e["name"] == "face":
+                polys = []
+                for r in rows:  # the index list is the first property of the face element in every file we read
+                    cnt = int(r[0])
+                    polys.append(np.array(r[1:1 + cnt], dtype=np.int64))
+                faces = fan(polys)
+    elif fmt in ("binary_little_endian", "binary_big_endian"):
+        bo = "<" if fmt == "binary_little_endian" else ">"
+        off = 0
+        for e in elements:
+            if any(p[1] == "list" for p in e["props"]):
+                polys = []
+                for _ in range(e["count"]):
+                    for name, kind, ct, it in e["props"]:
+                        if kind == "list":
+                            cnt = int(np.frombuffer(body, bo + ct, 1, off)[0])
+                            off += np.dtype(ct).itemsize
+                            vals = np.frombuffer(body, bo + it, cnt, off)
+                            off += cnt * np.dtype(it).itemsize
+                            if e["name"] == "face" and name in ("vertex_indices", "vertex_index"):
+                                polys.append(vals.astype(np.int64))
+                        else:
+                            off += np.dtype(kind).itemsize
+                if e["name"] == "face":
+                    faces = fan(polys)
+                continue
+            dt = np.dtype([(p[0], bo + p[1]) for p in e["props"]])
+            rec = np.frombuffer(body, dt, e["count"], off)
+            off += dt.itemsize * e["count"]
+            if e["name"] == "vertex":
+                names = [p[0] for p in e["props"]]
+                verts, cols = vertex_arrays(lambda k: names if k is None else rec[k])
+    else:
+        raise ValueError("unknown PLY format %r" % fmt)
+    return np.ascontiguousarray(verts, dtype=np.float64), np.ascontiguousarray(faces, dtype=np.int64), cols
+
+
+def write_ply_points(path, xyz, rgb=None):
+    """Binary little-endian PLY point cloud: double x / y / z, uchar red / green / blue (what open3d's write_point_cloud
+    writes for utils/reproj_filter.py:293-300)."""
+    xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+    hdr = ["ply", "format binary_little_endian 1.0", "element vertex %d" % xyz.shape[0], "property double x",
+           "property double y", "property double z"]
+    if rgb is not None:
+        hdr += ["property uchar red", "property uchar green", "property uchar blue"]
+    hdr.append("end_header")
+    rec = np.empty(xyz.shape[0], dtype=[("p", "<f8", 3)] + ([("c", "u1", 3)] if rgb is not None else []))
+    rec["p"] = xyz
+    if rgb is not None:
+        rec["c"] = np.asarray(rgb).reshape(-1, 3)
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(hdr) + "\n").encode("ascii"))
+        fh.write(rec.tobytes())
+
+
+# ---------------------------------------------------------------------------------------------------
+# the rasterizer (csrc/ncw_raster.hip)
+# ---------------------------------------------------------------------------------------------------
+class RasterMesh:
+    """A triangle mesh on the device, ready for `render`: vertices recentred in float64 and cast to f32 (the view's
+    translation absorbs the centre), faces int32, and the large-triangle list (2 entries per face: a face clipped by the
+    near plane has two sub-triangles)."""
+
+    def __init__(self, verts, faces, device=None):
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise L.NeuconwHipError("reproj.RasterMesh: the rasterizer runs on a GPU only; there is no CPU fallback")
+        v = torch.as_tensor(np.asarray(verts.detach().cpu() if torch.is_tensor(verts) else verts, dtype=np.float64)).reshape(-1, 3)
+        f = torch.as_tensor(np.asarray(faces.detach().cpu() if torch.is_tensor(faces) else faces, dtype=np.int64)).reshape(-1, 3)
+        if f.shape[0] >= (1 << 30):
+            raise ValueError("reproj.RasterMesh: at most 2^30 - 1 faces")
+        self.centre = ((v.amin(0) + v.amax(0)) / 2).numpy() if v.shape[0] else np.zeros(3)
+        self.dev = dev
+        self.nv, self.nf = int(v.shape[0]), int(f.shape[0])
+        self.verts = (v - torch.from_numpy(self.centre)).float().contiguous().to(dev)
+        self.faces = f.to(torch.int32).contiguous().to(dev)
+        self.large = torch.empty(max(1, 2 * self.nf), dtype=torch.int32, device=dev)
+        self.n_large = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def view_struct(self, K, view, height, width, znear=ZNEAR, zfar=ZFAR, cull="back", small_max=SMALL_MAX):
+        """NcwRasterView of a 3x4 / 4x4 world -> camera matrix `view` (float64, applied to the mesh's own frame): the centre
+        moves into the translation in float64, then everything is rounded to f32."""
+        if cull not in CULL:
+            raise ValueError("cull must be 'back' or 'none' (got %r)" % (cull,))
+        V = np.asarray(view, dtype=np.float64)[:3, :4].copy()
+        V[:, 3] = V[:, :3] @ self.centre + V[:, 3]
+        K = np.asarray(K, dtype=np.float64)
+        s = L.NcwRasterView()
+        for i, x in enumerate(V.reshape(-1)):
+            s.view[i] = float(x)
+        s.fx, s.fy, s.cx, s.cy = float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
+        s.znear, s.zfar = float(znear), float(zfar)
+        s.height, s.width = int(height), int(width)
+        s.cull = CULL[cull]
+        s.small_max = int(small_max)
+        return s
+
+    def rasterize(self, s, zbuf, timer=None):
+        """The z-buffer of one view into zbuf (int64 [H*W], overwritten).  timer: optional callable(stage) bracketing the
+        two raster kernels (scripts/bench_reproj.py)."""
+        lib = L.get_lib()
+        st = L.stream_ptr(self.dev)
+        zbuf.fill_(-1)  # all ones = empty
+        self.n_large.zero_()
+        if self.nf == 0:
+            return
+        if timer:
+            timer("small")
+        L.check(lib.ncw_raster_small(L.ptr(self.verts), self.nv, L.ptr(self.faces), self.nf, C.byref(s), L.ptr(zbuf),
+                                     L.ptr(self.large), L.ptr(self.n_large), st), "ncw_raster_small")
+        if timer:
+            timer("large")
+        L.check(lib.ncw_raster_large(L.ptr(self.verts), self.nv, L.ptr(self.faces), C.byref(s), L.ptr(self.large),
+                                     L.ptr(self.n_large), int(self.large.shape[0]), L.ptr(zbuf), st), "ncw_raster_large")
+        if timer:
+            timer("end")
+
+
+def resolve(zbuf, height, width, with_face=True):
+    """(depth [H,W] f32, 0 = empty; face [H,W] int32, -1 = empty, or None) of a z-buffer."""
+    lib = L.get_lib()
+    n = int(height) * int(width)
+    depth = torch.empty(n, dtype=torch.float32, device=zbuf.device)
+    face = torch.empty(n, dtype=torch.int32, device=zbuf.device) if with_face else None
+    L.check(lib.ncw_raster_resolve(L.ptr(zbuf), n, L.ptr(depth), L.ptr(face), L.stream_ptr(zbuf.device)), "ncw_raster_resolve")
+    return depth.view(height, width), (face.view(height, width) if with_face else None)
+
+
+@torch.no_grad()
+def render_depth(verts, faces, K, view, height, width, znear=ZNEAR, zfar=ZFAR, cull="back", device=None, small_max=SMALL_MAX,
+                 stats=None):
+    """Linear eye-space depth of the mesh (verts [V,3], faces [F,3]; numpy or torch) seen by the pinhole camera K (3x3:
+    fx, fy, cx, cy) at world -> camera `view` (3x4 or 4x4, OpenCV axes), as pyrender renders it for
+    utils/pyrender_renderer.py: pixel (r, c) samples the image point (c + 0.5, r + 0.5), near-plane clipping, samples beyond
+    zfar dropped, back faces culled (cull='back') or not ('none').  Returns (depth [H,W] f32, 0 where nothing is hit;
+    face [H,W] int32, -1 there) on the device.  stats (dict): `large` = sub-triangles that took the workgroup path."""
+    m = RasterMesh(verts, faces, device)
+    s = m.view_struct(K, view, height, width, znear, zfar, cull, small_max)
+    zbuf = torch.empty(int(height) * int(width), dtype=torch.int64, device=m.dev)
+    m.rasterize(s, zbuf)
+    if stats is not None:
+        stats["large"] = int(m.n_large.item())
+    return resolve(zbuf, int(height), int(width))
+
+
+def backproject(depth, M):
+    """Points [N,3] f32 of the pixels with depth > 0, in pixel order: M[:, :3] (c d, r d, d) + M[:, 3] (M 3x4 on the host,
+    rounded to f32), and their linear pixel indices [N] int64."""
+    lib = L.get_lib()
+    h, w = depth.shape
+    flat = depth.reshape(-1).contiguous()
+    pix = torch.nonzero(flat > 0).reshape(-1).contiguous()  # pixel order; one device -> host read (the count)
+    n = int(pix.shape[0])
+    pts = torch.empty(n, 3, dtype=torch.float32, device=depth.device)
+    Mf = (C.c_float * 12)(*[float(x) for x in np.asarray(M, dtype=np.float64)[:3, :4].reshape(-1)])
+    L.check(lib.ncw_raster_backproject(L.ptr(flat), L.ptr(pix), n, int(w), Mf, L.ptr(pts), L.stream_ptr(depth.device)),
+            "ncw_raster_backproject")
+    return pts, pix
+
+
+def backproject_matrix(K, pose, centre=None):
+    """3x4 float64 M with M[:, :3] (c d, r d, d) + M[:, 3] = pose[:3] [K^-1 (c, r, 1) d; 1] - centre
+    (utils/reproj_filter.py:133-152)."""
+    pose = np.asarray(pose, dtype=np.float64)
+    M = np.zeros((3, 4))
+    M[:, :3] = pose[:3, :3] @ np.linalg.inv(np.asarray(K, dtype=np.float64))
+    M[:, 3] = pose[:3, 3] - (0.0 if centre is None else np.asarray(centre, dtype=np.float64))
+    return M
+
+
+# ---------------------------------------------------------------------------------------------------
+# the filter (utils/reproj_filter.py)
+# ---------------------------------------------------------------------------------------------------
+class Target:
+    """The cloud to filter (utils/reproj_filter.py:177-189): every vertex of target_file (no welding) in GT coordinates,
+    its colours (zeros without), and one NNGrid over it (recentred on its box centre in float64, as nn_distances does)."""
+
+    def __init__(self, xyz, rgb, thr, device):
+        self.xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        self.rgb = np.zeros(self.xyz.shape, dtype=np.uint8) if rgb is None else np.asarray(rgb, dtype=np.uint8).reshape(-1, 3)
+        self.m = self.xyz.shape[0]
+        self.dev = device
+        self.thr = float(thr)
+        self.flags = torch.zeros(max(1, self.m), dtype=torch.uint8, device=device)
+        self.centre = (self.xyz.min(0) + self.xyz.max(0)) / 2 if self.m else np.zeros(3)
+        self.grid = None
+        if self.m:
+            r32 = torch.from_numpy(self.xyz - self.centre).float().to(device).contiguous()
+            # queries further than thr outside the cloud's box can mark nothing: the stop test's rounding margin needs to
+            # cover the coordinates of the cloud and of the queries that can
+            cmax = float(r32.abs().max()) + self.thr
+            self.grid = evalmesh.NNGrid(r32, cmax)
+
+    def mark(self, pts32):
+        """Marks the nearest target vertex of every query closer than thr (queries: recentred f32 [N,3])."""
+        n = int(pts32.shape[0])
+        if n == 0 or self.grid is None:
+            return
+        dist, idx = self.grid.query(pts32)
+        L.check(L.get_lib().ncw_raster_mark(L.ptr(dist), L.ptr(idx), n, self.thr, self.m, L.ptr(self.flags),
+                                            L.stream_ptr(self.dev)), "ncw_raster_mark")
+
+    def rows(self):
+        """np.unique over the rows [xyz, rgb] of the marked vertices (lexicographic): (xyz float64, rgb uint8)."""
+        keep = torch.nonzero(self.flags[: self.m]).reshape(-1).cpu().numpy()
+        if keep.shape[0] == 0:
+            return np.zeros((0, 3)), np.zeros((0, 3), dtype=np.uint8)
+        rows = np.concatenate([self.xyz[keep], self.rgb[keep].astype(np.float64)], 1)
+        u = torch.unique(torch.from_numpy(rows).to(self.dev), dim=0).cpu().numpy()  # sorted rows, as np.unique(axis=0)
+        return u[:, :3].copy(), u[:, 3:].astype(np.uint8)
+
+
+@torch.no_grad()
+def reproj_filter(src_file, target_file, data_path, output_path, gt=False, voxel_size=0.01, visualize=False, znear=ZNEAR,
+                  zfar=ZFAR, cull="back", device=None, verbose=True):
+    """utils/reproj_filter.py: keep the vertices of target_file that a training view of data_path sees on src_file's mesh.
+    Per view: render the depth of the source mesh, back-project every pixel with depth > 0 at its integer pixel coordinates,
+    mark the nearest target vertex when it is closer than 2 sqrt(2) voxel_size (GT units).  Both files are carried to GT
+    coordinates by config.yaml's sfm2gt unless `gt`.  Writes <output_path>/reprojected.ply (np.unique of the marked rows
+    [xyz, rgb], double xyz + uchar colours); `visualize` also writes render/depth/<name>.npy and render/reprojects/<name>.ply.
+    Returns (xyz float64 [K,3], rgb uint8 [K,3])."""
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    log = print if verbose else (lambda *a, **k: None)
+    os.makedirs(output_path, exist_ok=True)
+    log("result will be saved to %s" % output_path)
+    S = read_sfm2gt(data_path)
+    views = load_views(data_path, S)
+    log("views to process: %d" % len(views))
+
+    t_xyz, _, t_rgb = read_ply_mesh(target_file)
+    if not gt:
+        t_xyz = evalmesh.apply_transform(t_xyz, S)
+    if t_rgb is None:
+        log("No color found in target point cloud")
+    target = Target(t_xyz, t_rgb, 2 * np.sqrt(2) * voxel_size, dev)
+
+    s_verts, s_faces, _ = read_ply_mesh(src_file)
+    if s_faces.shape[0] == 0:
+        raise ValueError("%s has no faces: the point-cloud source (the reference's kaolin renderer) is not supported" % src_file)
+    mesh = RasterMesh(s_verts, s_faces, dev)
+    zbuf = None
+    for v in views:
+        w, h = v["wh"]
+        # the source mesh is rasterized in its file's frame: with E (SfM frame) unless gt, else with E inv(sfm2gt) -- the
+        # reference's render of the GT-frame mesh with E inv(sfm2gt) in both cases, up to rounding
+        s = mesh.view_struct(v["K"], v["E_gt"] if gt else v["E"], h, w, znear, zfar, cull)
+        if zbuf is None or zbuf.numel() != h * w:
+            zbuf = torch.empty(h * w, dtype=torch.int64, device=dev)
+        mesh.rasterize(s, zbuf)
+        depth, _ = resolve(zbuf, h, w, with_face=False)
+        pts, _ = backproject(depth, backproject_matrix(v["K"], v["pose"], target.centre))
+        target.mark(pts)
+        if pts.shape[0] < 10:
+            log("[WARNING] invalid view at %s" % v["name"])
+        if visualize:
+            stem = os.path.splitext(v["name"])[0]
+            for sub in ("depth", "reprojects"):
+                os.makedirs(os.path.join(output_path, "render", sub), exist_ok=True)
+            np.save(os.path.join(output_path, "render", "depth", stem + ".npy"), depth.cpu().numpy())
+            write_ply_points(os.path.join(output_path, "render", "reprojects", stem + ".ply"),
+                             pts.double().cpu().numpy() + target.centre)
+    xyz, rgb = target.rows()
+    write_ply_points(os.path.join(output_path, "reprojected.ply"), xyz, rgb)
+    log("kept %d of %d vertices" % (xyz.shape[0], target.m))
+    return xyz, rgb
+
+
+# ---------------------------------------------------------------------------------------------------
+# scripts/eval_pipeline.sh
+# ---------------------------------------------------------------------------------------------------
+# per scene: F-score thresholds, SfM crop track length / reprojection error / voxel size (scripts/eval_pipeline.sh:22-53)
+SCENES = {
+    "brandenburg_gate": {"thresholds": "0.01,1,0.01", "track_length": 14, "reproj_error": 2.0, "voxel_size": 2.0},
+    "lincoln_memorial": {"thresholds": "0.005,0.3,0.005", "track_length": 12, "reproj_error": 1.6, "voxel_size": 0.04},
+    "palacio_de_bellas_artes": {"thresholds": "0.01,1,0.01", "track_length": 12, "reproj_error": 1.5, "voxel_size": 2.0},
+    "pantheon_exterior": {"thresholds": "0.01,1,0.01", "track_length": 12, "reproj_error": 1.4, "voxel_size": 0.1},
+}
+
+
+def eval_pipeline(scene_name, pred_dir, data_root="data/heritage-recon", verbose=True):
+    """scripts/eval_pipeline.sh in one process: the reprojection filter of <pred_dir>/mesh/extracted_mesh_level_10_colored.ply
+    against itself (written to <pred_dir>/mesh/reprojected.ply), then evalmesh.eval_mesh of that file against
+    <data_root>/<scene>/<scene>.ply with the scene's thresholds and the SfM crop of <data_root>/<scene>/neuralsfm, results in
+    <pred_dir>/mesh/eval_<scene>_reprojected.ply/.  Returns the last threshold's metrics."""
+    if scene_name not in SCENES:
+        raise ValueError("Not supported scene: %s (one of %s)" % (scene_name, ", ".join(sorted(SCENES))))
+    sc = SCENES[scene_name]
+    pred_path = os.path.join(pred_dir, "mesh")
+    scene_dir = os.path.join(data_root, scene_name)
+    mesh_file = os.path.join(pred_path, "extracted_mesh_level_10_colored.ply")
+    reproj_filter(mesh_file, mesh_file, scene_dir, pred_path, verbose=verbose)
+    with open(os.path.join(scene_dir, "config.yaml")) as fh:
+        scene_config = yaml.safe_load(fh)
+    sfm = {"path": os.path.join(scene_dir, "neuralsfm"), "track_length": sc["track_length"],
+           "reproj_error": sc["reproj_error"], "voxel_size": sc["voxel_size"]}
+    return evalmesh.eval_mesh(os.path.join(pred_path, "reprojected.ply"), os.path.join(scene_dir, scene_name + ".ply"),
+                              scene_config, False, threshold=evalmesh.parse_thresholds(sc["thresholds"]), bbx_name="eval_bbx",
+                              save_name=scene_name + "_reprojected.ply", sfm=sfm, verbose=verbose)

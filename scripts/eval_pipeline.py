@@ -1,0 +1,36 @@
+"""Evaluation pipeline of one Heritage-Recon scene: the reference's `scripts/eval_pipeline.sh` in one
+process -- the reprojection filter of the extracted mesh (scripts/reproj_filter.py), then the F-score of what it keeps
+(scripts/eval_mesh.py) with the scene's thresholds and SfM crop.
+
+    python scripts/eval_pipeline.py --scene_name brandenburg_gate --pred_dir results/phototourism/<run> \
+        [--data_root data/heritage-recon]
+
+Reads <pred_dir>/mesh/extracted_mesh_level_10_colored.ply, <data_root>/<scene>/{dense/sparse, *.tsv, config.yaml,
+<scene>.ply, neuralsfm/points3D.bin}; writes <pred_dir>/mesh/reprojected.ply and
+<pred_dir>/mesh/eval_<scene>_reprojected.ply/.  As in the reference, eval_mesh applies sfm2gt to the filtered cloud that is
+already in GT coordinates: the two steps chain correctly only when sfm2gt is the identity.
+"""
+import argparse
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from neuralrecon_w_amd import reproj  # noqa: E402
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description="reprojection filter + mesh evaluation of a Heritage-Recon scene")
+    ap.add_argument("--scene_name", required=True, choices=sorted(reproj.SCENES))
+    ap.add_argument("--pred_dir", required=True, help="run directory holding mesh/extracted_mesh_level_10_colored.ply")
+    ap.add_argument("--data_root", default="data/heritage-recon", help="Heritage-Recon root")
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    print("Evaluating %s ..." % args.pred_dir)
+    reproj.eval_pipeline(args.scene_name, args.pred_dir, args.data_root)
+
+
+if __name__ == "__main__":
+    main()
