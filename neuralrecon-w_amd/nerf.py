@@ -8,9 +8,9 @@ import torch
 from torch import nn
 
 from . import lib as L
-from .neuconw import _PackedNet, _wvb, default_prec, points_struct
-from .packing import PackPlan
-from .stash import StashArena, StashCache
+from .neuconw import default_prec, points_struct, ray_head_bias
+from .packing import PackPlan, _PackedNet
+from .stash import StashCache, build_stash
 
 
 class NeRF(_PackedNet):
@@ -53,7 +53,7 @@ class NeRF(_PackedNet):
     def n_head(self):
         return len(self.apperence_encoding)
 
-    def _plan_switches(self):
+    def _plan_switches(self, prec):
         return (bool(self.refine),)
 
     def _build_plan(self, prec, dev):
@@ -64,60 +64,41 @@ class NeRF(_PackedNet):
 
         split = prec == L.PREC_F16 and self.refine and RBN == 8  # residual matrices of the forward (ncw_nerf_refine)
 
-        def full(name, mod, rb_out, rb_in, segs):
-            v, g, b = _wvb(mod)
-            m, bs, mt = plan.new_matrix(rb_out, rb_in), plan.new_bias(rb_out), plan.new_matrix(rb_in, rb_out)
-            dn = plan.new_dense_grad(rb_out, rb_in)
-            plan.add_pack(v, g, b, m, bs, segs)
-            plan.add_pack(v, g, None, mt, None, segs, transpose=True)
-            plan.add_unpack(v, g, b, dn, segs)
-            lo = None
-            if split:
-                lo = plan.new_matrix(rb_out, rb_in)
-                plan.add_pack(v, g, None, lo, None, segs, residual=True)
-            sl[name] = (m, bs, mt, dn, lo)
-
-        full("p0", self.pts_linears[0], RBN, 3, [(0, E, 0)])
+        sl["p0"] = plan.add_linear(self.pts_linears[0], RBN, 3, [(0, E, 0)], lo=split)
         for i in range(1, self.D):
             if i == self.skips[0] + 1:  # input = cat([gamma(p), h])  (nerf.py:166-167)
-                full("p%d" % i, self.pts_linears[i], RBN, RBN + 3, [(E, W, 0), (0, E, 32 * RBN)])
+                sl["p%d" % i] = plan.add_linear(self.pts_linears[i], RBN, RBN + 3, [(E, W, 0), (0, E, 32 * RBN)], lo=split)
             else:
-                full("p%d" % i, self.pts_linears[i], RBN, RBN, [(0, W, 0)])
-        full("alpha", self.alpha_linear, 1, RBN, [(0, W, 0)])
-        full("feat", self.feature_linear, RBN, RBN, [(0, W, 0)])
-        full("a0", self.apperence_encoding[0], RBH, RBN + 3, [(0, W, 0), (W, 27 + A, 32 * RBN)])
+                sl["p%d" % i] = plan.add_linear(self.pts_linears[i], RBN, RBN, [(0, W, 0)], lo=split)
+        sl["alpha"] = plan.add_linear(self.alpha_linear, 1, RBN, [(0, W, 0)], lo=split)
+        sl["feat"] = plan.add_linear(self.feature_linear, RBN, RBN, [(0, W, 0)], lo=split)
+        sl["a0"] = plan.add_linear(self.apperence_encoding[0], RBH, RBN + 3, [(0, W, 0), (W, 27 + A, 32 * RBN)], lo=split)
         for i in range(1, self.n_head):
-            full("a%d" % i, self.apperence_encoding[i], RBH, RBH, [(0, W // 2, 0)])
-        full("rgb", self.rgb_linear, 1, RBH, [(0, W // 2, 0)])
+            sl["a%d" % i] = plan.add_linear(self.apperence_encoding[i], RBH, RBH, [(0, W // 2, 0)], lo=split)
+        sl["rgb"] = plan.add_linear(self.rgb_linear, 1, RBH, [(0, W // 2, 0)], lo=split)
         plan.finalize()
-
-        def trip(name):
-            s = sl[name]
-            return plan.mat_ptr(s[0]), plan.bias_ptr(s[1]), plan.mat_ptr(s[2])
-
         for i in range(self.D):
-            net.w_p[i], net.b_p[i], net.wt_p[i] = trip("p%d" % i)
-        net.w_alpha, net.b_alpha, net.wt_alpha = trip("alpha")
-        net.w_feat, net.b_feat, net.wt_feat = trip("feat")
+            net.w_p[i], net.b_p[i], net.wt_p[i] = plan.wb_ptrs(sl["p%d" % i])
+            net.w_p_lo[i] = plan.mat_ptr(sl["p%d" % i].lo)
         for i in range(self.n_head):
-            net.w_a[i], net.b_a[i], net.wt_a[i] = trip("a%d" % i)
-        net.w_rgb, net.b_rgb, net.wt_rgb = trip("rgb")
-        if split:
-            for i in range(self.D):
-                net.w_p_lo[i] = plan.mat_ptr(sl["p%d" % i][4])
-            for i in range(self.n_head):
-                net.w_a_lo[i] = plan.mat_ptr(sl["a%d" % i][4])
-            net.w_alpha_lo, net.w_feat_lo, net.w_rgb_lo = (plan.mat_ptr(sl[k][4]) for k in ("alpha", "feat", "rgb"))
+            net.w_a[i], net.b_a[i], net.wt_a[i] = plan.wb_ptrs(sl["a%d" % i])
+            net.w_a_lo[i] = plan.mat_ptr(sl["a%d" % i].lo)
+        net.w_alpha, net.b_alpha, net.wt_alpha = plan.wb_ptrs(sl["alpha"])
+        net.w_feat, net.b_feat, net.wt_feat = plan.wb_ptrs(sl["feat"])
+        net.w_rgb, net.b_rgb, net.wt_rgb = plan.wb_ptrs(sl["rgb"])
+        net.w_alpha_lo, net.w_feat_lo, net.w_rgb_lo = (plan.mat_ptr(sl[k].lo) for k in ("alpha", "feat", "rgb"))
         plan.has_lo = split
         net.D, net.skip, net.rbn, net.rbh, net.n_head, net.n_a = self.D, self.skips[0], RBN, RBH, self.n_head, A
         plan.net, plan.slots = net, sl
         return plan
 
-    def supports_selection(self, prec):
-        """Point selections (NcwPoints mode 4, dead-background elimination): every background kernel takes them (the
-        W = 256 16-bit weights-stationary kernels, and the generic weights-through-LDS kernels of the fp32 parity mode /
-        other widths / the reproducible d_a_rows path)."""
-        return True
+    def _stash_fields(self, train):
+        RBN, RBH = self.W // 32, self.W // 64
+        if not train:
+            return []
+        return [("gp", 3), ("aux1", 3), ("featn", RBN), ("zalpha", 1), ("zfeat", RBN), ("zrgb", 1),
+                ("h", {i: RBN for i in range(1, self.D + 1)}), ("zp", [RBN] * self.D), ("e", [RBH] * self.n_head),
+                ("ze", [RBH] * self.n_head)]
 
     def fwd_stash(self, pts, n, prec, a, x4=None, select=None, train=True, refine=None):
         """refine = (z, O) (like `select`; fp16 mode at W = 256 with .refine on): after the plain forward the samples the compositor
@@ -132,32 +113,8 @@ class NeRF(_PackedNet):
         weight-gradient products are sized by the device count ctx["sel_count"]."""
         dev = self._first_param().device
         plan = self.packed(prec)
-        RBN, RBH = self.W // 32, self.W // 64
-
-        def build_render():
-            return dict(arena=StashArena(dev, prec, n).allocate(), ids={}, stash=L.NcwNerfStash())
-
-        def build():
-            ar = StashArena(dev, prec, n)
-            ids = dict(gp=ar.new(3), aux1=ar.new(3), featn=ar.new(RBN), zalpha=ar.new(1), zfeat=ar.new(RBN),
-                       zrgb=ar.new(1))
-            ids["h"] = {i: ar.new(RBN) for i in range(1, self.D + 1)}
-            ids["zp"] = [ar.new(RBN) for _ in range(self.D)]
-            ids["e"] = [ar.new(RBH) for _ in range(self.n_head)]
-            ids["ze"] = [ar.new(RBH) for _ in range(self.n_head)]
-            ar.allocate()
-            st = L.NcwNerfStash()
-            for k in ("gp", "aux1", "featn", "zalpha", "zfeat", "zrgb"):
-                setattr(st, k, ar.ptr(ids[k]))
-            for i, v in ids["h"].items():
-                st.h[i] = ar.ptr(v)
-            for k in ("zp", "e", "ze"):
-                for i, v in enumerate(ids[k]):
-                    getattr(st, k)[i] = ar.ptr(v)
-            return dict(arena=ar, ids=ids, stash=st)
-
-        ent = self.__dict__.setdefault("_stash_cache", StashCache()).acquire((prec, n, str(dev), bool(train)),
-                                                                             build if train else build_render)
+        ent = self.__dict__.setdefault("_stash_cache", StashCache()).acquire(
+            (prec, n, str(dev), bool(train)), lambda: build_stash(L.NcwNerfStash, self._stash_fields(train), dev, prec, n))
         ar, ids, st = ent["arena"], ent["ids"], ent["stash"]
         sel_count = None
         do_refine = (refine is not None and prec == L.PREC_F16 and self.refine and getattr(plan, "has_lo", False) and x4 is None)
@@ -166,7 +123,7 @@ class NeRF(_PackedNet):
             z_prim, O_ = select if select is not None else refine
             z_prim = z_prim.contiguous().float()
             S_ = int(z_prim.shape[1])
-            assert x4 is None and pts.mode == 2 and pts.per_ray == S_ + O_ and self.supports_selection(prec)
+            assert x4 is None and pts.mode == 2 and pts.per_ray == S_ + O_
             if "sel_idx" not in ent:  # per lease: the weight-gradient table caches the count's address
                 ent["sel_idx"] = torch.empty(n, device=dev, dtype=torch.int32)
                 ent["sel_count"] = torch.zeros(1, device=dev, dtype=torch.int32)
@@ -201,20 +158,7 @@ class NeRF(_PackedNet):
             rgb = torch.empty(n, 3, device=dev, dtype=torch.float32)
         a = a.contiguous().float()
         x4c = x4.contiguous().float() if x4 is not None else None
-        # 16-bit modes: the appearance head's view-direction / appearance-code columns once per ray in fp32 (as
-        # RenderingNetwork.fwd_stash; models/nerf.py:131-139,173-174).  Forward only.
-        st.aux_bias = None
-        lin0 = self.apperence_encoding[0]
-        if prec != L.PREC_F32 and self.ray_bias and pts.rays_d and hasattr(lin0, "weight"):
-            R, no = a.shape[0], 32 * RBH
-            ab = ent.get("aux_bias")
-            if ab is None or ab.shape[0] != R:
-                ab = ent["aux_bias"] = torch.empty(R, no, device=dev, dtype=torch.float32)
-            w0 = lin0.weight.detach()
-            assert w0.is_contiguous() and w0.dtype == torch.float32 and w0.shape == (self.W // 2, self.W + 27 + self.in_channels_a)
-            L.check(L.get_lib().ncw_aux_ray_bias(L.ptr(w0), w0.shape[1], self.W, self.W // 2, ctypes.c_void_p(pts.rays_d), L.ptr(a),
-                                                 self.in_channels_a, R, L.ptr(ab), no, L.stream_ptr(dev)), "ncw_aux_ray_bias")
-            st.aux_bias = ab.data_ptr()
+        ray_head_bias(st, ent, self.apperence_encoding[0], self.ray_bias, prec, pts, a, self.W, self.W // 2, self.in_channels_a)
         L.check(L.get_lib().ncw_nerf_fwd(plan.net, prec, pts, L.ptr(x4c), n, L.ptr(a), L.ptr(density), L.ptr(rgb), st,
                                          L.stream_ptr(dev)), "ncw_nerf_fwd")
         if do_refine and st.aux_bias:  # (the head's per-ray fp32 columns are its input: .ray_bias on)
@@ -239,29 +183,25 @@ class NeRF(_PackedNet):
         RBN, RBH = self.W // 32, self.W // 64
         P = ar.ptr
 
-        def dn(name):
-            d = sl[name][3]
-            return plan.dense_ptr(d), plan.dense_ld(d), plan.dense_bias_ptr(d)
-
-        dp, ld, db = dn("p0")
+        dp, ld, db = plan.dense_ptrs(sl["p0"])
         batch.add(P(ids["zp"][0]), RBN, P(ids["gp"]), 3, dp, ld, db)
         for i in range(1, self.D):
-            dp, ld, db = dn("p%d" % i)
+            dp, ld, db = plan.dense_ptrs(sl["p%d" % i])
             batch.add(P(ids["zp"][i]), RBN, P(ids["h"][i]), RBN, dp, ld, db)
             if i == self.skips[0] + 1:
                 batch.add(P(ids["zp"][i]), RBN, P(ids["gp"]), 3, dp + 4 * 32 * RBN, ld)
         hD = P(ids["h"][self.D])
-        dp, ld, db = dn("alpha")
+        dp, ld, db = plan.dense_ptrs(sl["alpha"])
         batch.add(P(ids["zalpha"]), 1, hD, RBN, dp, ld, db)
-        dp, ld, db = dn("feat")
+        dp, ld, db = plan.dense_ptrs(sl["feat"])
         batch.add(P(ids["zfeat"]), RBN, hD, RBN, dp, ld, db)
-        dp, ld, db = dn("a0")
+        dp, ld, db = plan.dense_ptrs(sl["a0"])
         batch.add(P(ids["ze"][0]), RBH, P(ids["featn"]), RBN, dp, ld, db)
         batch.add(P(ids["ze"][0]), RBH, P(ids["aux1"]), 3, dp + 4 * 32 * RBN, ld)
         for i in range(1, self.n_head):
-            dp, ld, db = dn("a%d" % i)
+            dp, ld, db = plan.dense_ptrs(sl["a%d" % i])
             batch.add(P(ids["ze"][i]), RBH, P(ids["e"][i - 1]), RBH, dp, ld, db)
-        dp, ld, db = dn("rgb")
+        dp, ld, db = plan.dense_ptrs(sl["rgb"])
         batch.add(P(ids["zrgb"]), 1, P(ids["e"][self.n_head - 1]), RBH, dp, ld, db)
 
     @torch.no_grad()

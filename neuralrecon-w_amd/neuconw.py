@@ -13,8 +13,8 @@ import torch
 from torch import nn
 
 from . import lib as L
-from .packing import PackPlan
-from .stash import StashArena, StashCache
+from .packing import PackPlan, _PackedNet
+from .stash import StashCache, build_stash
 
 
 def points_struct(x=None, rays_o=None, rays_d=None, z=None, sample_dist=None, mode=0, idx=None, count=None):
@@ -41,6 +41,26 @@ def points_struct(x=None, rays_o=None, rays_d=None, z=None, sample_dist=None, mo
     return p
 
 
+def ray_head_bias(st, lease, lin0, on, prec, pts, a, d_feat, n_out, n_a):
+    """16-bit modes: the per-RAY part of an appearance head's first layer -- W[:, view-dir | appearance columns] . [gamma_4(d) | a]
+    (models/neuconw.py:131-140, models/nerf.py:131-139,173-174) -- is evaluated once per ray in fp32 (ncw_aux_ray_bias) and added
+    to that layer's bias; rounding `a` and gamma(d) to 16 bits is coherent along a ray and was the largest term of the fp16 mode's
+    colour error on trained weights (scripts/diag/emul_color16.py).  Forward only: the backward / weight gradients are unchanged.
+    Sets st.aux_bias (NULL: `on` off, fp32, no ray directions or a weight-normed `lin0`); the buffer lives on the lease."""
+    st.aux_bias = None
+    if prec == L.PREC_F32 or not on or not pts.rays_d or hasattr(lin0, "weight_v"):
+        return
+    R, no = a.shape[0], (n_out + 31) // 32 * 32
+    ab = lease.get("aux_bias")
+    if ab is None or ab.shape[0] != R:
+        ab = lease["aux_bias"] = torch.empty(R, no, device=a.device, dtype=torch.float32)
+    w0 = lin0.weight.detach()
+    assert w0.is_contiguous() and w0.dtype == torch.float32 and w0.shape == (n_out, d_feat + 27 + n_a)
+    L.check(L.get_lib().ncw_aux_ray_bias(L.ptr(w0), w0.shape[1], d_feat, n_out, ctypes.c_void_p(pts.rays_d), L.ptr(a), n_a, R,
+                                         L.ptr(ab), no, L.stream_ptr(a.device)), "ncw_aux_ray_bias")
+    st.aux_bias = ab.data_ptr()
+
+
 class WNLinear(nn.Module):
     """Parameter holder with the state_dict layout of nn.utils.weight_norm(nn.Linear)
     (keys bias, weight_g [out,1], weight_v [out,in]; models/neuconw.py:104-105,256-257)."""
@@ -60,13 +80,6 @@ class PlainLinear(nn.Module):
         self.in_features, self.out_features = lin.in_features, lin.out_features
         self.weight = nn.Parameter(lin.weight.detach().clone())
         self.bias = nn.Parameter(lin.bias.detach().clone())
-
-
-def _wvb(m):
-    """(weight-or-v, g-or-None, bias) of a WNLinear / PlainLinear / nn.Linear."""
-    if hasattr(m, "weight_v"):
-        return m.weight_v, m.weight_g, m.bias
-    return m.weight, None, m.bias
 
 
 def _prec_of(v):
@@ -102,7 +115,7 @@ def default_infer_prec():
     return _prec_of(os.environ.get("NEUCONW_INFER_PREC", "f32"))
 
 
-class SDFNetwork(nn.Module):
+class SDFNetwork(_PackedNet):
     """models/neuconw.py:183-296.  d_in must be 3, multires 6 (the only shipped encoding)."""
 
     def __init__(self, d_in, d_out, d_hidden, n_layers, skip_in=(4,), multires=6, bias=0.5, scale=1,
@@ -145,7 +158,7 @@ class SDFNetwork(nn.Module):
                     torch.nn.init.constant_(lin.bias, 0.0)
                     torch.nn.init.normal_(lin.weight, 0.0, np.sqrt(2) / np.sqrt(out_dim))
             setattr(self, "lin" + str(l), WNLinear(lin))
-        self._plans = {}
+        self._init_plans()
 
     # ---- pack plan --------------------------------------------------------------------------
     @property
@@ -175,19 +188,17 @@ class SDFNetwork(nn.Module):
             return _prec_of(env)
         return L.PREC_F16 if self.split_value(L.PREC_F16) else L.PREC_F32
 
-    def plan(self, prec):
-        dev = self.lin0.bias.device
+    def _plan_switches(self, prec):
+        return (self.split_value(prec), self.__dict__.get("adj_split"))
+
+    def _build_plan(self, prec, dev):
         split = self.split_value(prec)
-        key = (prec, str(dev), split, self.__dict__.get("adj_split"))
-        p = self._plans.get(key)
-        if p is not None:
-            return p
         RB, W, E = self.d_hidden // 32, self.d_hidden, self.d_enc
         Lm = self.n_lin
         skip = self.skip_in[0] if self.skip_in else -1
         plan = PackPlan(dev, prec)
         net = L.NcwSdfNet()
-        slots, lo, lo_t = {}, {}, {}
+        sl = {}
         # the adjoint sweep's transposed residuals (NcwSdfNet.wt_lo; csrc/ncw_split.hip sdf_fwdSA, ncw_sdf16.hip sdf_fwdS16<., ADJ>):
         # `.adj_split` / NEUCONW_SDF_ADJ_SPLIT = 0 | False: single-rounded operands in the adjoint sweep (round 4's kernels);
         # 1 | True: W^T as hi + lo pairs, t_l single fp16 (round 5); 2: t_l as a pair too (round 6, W = 512 only).
@@ -203,79 +214,27 @@ class SDFNetwork(nn.Module):
         if RB == 8:
             adj = min(adj, 1)
         for l in range(Lm):
-            v, g, b = _wvb(getattr(self, "lin%d" % l))
-            n_out, n_in = v.shape
+            mod = getattr(self, "lin%d" % l)
             if l == 0:
                 rb_in, segs, scale = 2, [(0, E, 0)], 1.0
             elif l == skip:
                 rb_in, segs, scale = RB + 2, [(0, W - E, 0), (W - E, E, 32 * RB)], 1.0 / math.sqrt(2.0)
             else:
-                rb_in, segs, scale = RB, [(0, n_in, 0)], 1.0
+                rb_in, segs, scale = RB, [(0, mod.in_features, 0)], 1.0
             if l < Lm - 1:
-                m, bs = plan.new_matrix(RB, rb_in), plan.new_bias(RB)
-                mt = plan.new_matrix(rb_in, RB)
-                dn = plan.new_dense_grad(RB, rb_in)
-                plan.add_pack(v, g, b, m, bs, segs, scale=scale)
-                plan.add_pack(v, g, None, mt, None, segs, transpose=True, scale=scale)
-                plan.add_unpack(v, g, b, dn, segs, scale=scale)
-                slots[l] = (m, bs, mt, dn)
-                if split:
-                    lo[l] = plan.new_matrix(RB, rb_in)
-                    plan.add_pack(v, g, None, lo[l], None, segs, scale=scale, residual=True)
-                if adj:
-                    lo_t[l] = plan.new_matrix(rb_in, RB)
-                    plan.add_pack(v, g, None, lo_t[l], None, segs, transpose=True, scale=scale, residual=True)
-            else:  # last Linear: row 0 = sdf, rows 1..W = feature vector (neuconw.py:279)
-                m, bs = plan.new_matrix(1, RB), plan.new_bias(1)
-                mt = plan.new_matrix(RB, 1)
-                mf, bf = plan.new_matrix(RB, RB), plan.new_bias(RB)
-                mft = plan.new_matrix(RB, RB)
-                dn = plan.new_dense_grad(1, RB)
-                dnf = plan.new_dense_grad(RB, RB)
-                plan.add_pack(v, g, b, m, bs, segs, row0=0, nrows=1)
-                plan.add_pack(v, g, None, mt, None, segs, row0=0, nrows=1, transpose=True)
-                plan.add_pack(v, g, b, mf, bf, segs, row0=1, nrows=W)
-                plan.add_pack(v, g, None, mft, None, segs, row0=1, nrows=W, transpose=True)
-                plan.add_unpack(v, g, b, dn, segs, row0=0, nrows=1)
-                plan.add_unpack(v, g, b, dnf, segs, row0=1, nrows=W)
-                slots[l] = (m, bs, mt, dn, mf, bf, mft, dnf)
-                if split:
-                    lo[l] = plan.new_matrix(1, RB)
-                    plan.add_pack(v, g, None, lo[l], None, segs, row0=0, nrows=1, residual=True)
-                if adj:
-                    lo_t[l] = plan.new_matrix(RB, 1)
-                    plan.add_pack(v, g, None, lo_t[l], None, segs, row0=0, nrows=1, transpose=True, residual=True)
+                sl[l] = plan.add_linear(mod, RB, rb_in, segs, scale=scale, lo=split, lo_t=adj)
+            else:  # last Linear: row 0 = sdf, rows 1..W = feature vector (neuconw.py:279); the sdf row's residuals come after both
+                sl[l] = plan.add_linear(mod, 1, RB, segs, row0=0, nrows=1)
+                sl["feat"] = plan.add_linear(mod, RB, RB, segs, row0=1, nrows=W)
+                sl[l] = plan.add_residuals(mod, sl[l], segs, row0=0, nrows=1, lo=split, lo_t=adj)
         plan.finalize()
-        for l, m_lo in lo.items():
-            net.w_lo[l] = plan.mat_ptr(m_lo)
-        for l, m_lo in lo_t.items():
-            net.wt_lo[l] = plan.mat_ptr(m_lo)
         for l in range(Lm):
-            s = slots[l]
-            net.w[l], net.b[l], net.wt[l] = plan.mat_ptr(s[0]), plan.bias_ptr(s[1]), plan.mat_ptr(s[2])
-        s = slots[Lm - 1]
-        net.w_feat, net.b_feat, net.wt_feat = plan.mat_ptr(s[4]), plan.bias_ptr(s[5]), plan.mat_ptr(s[6])
+            net.w[l], net.b[l], net.wt[l] = plan.wb_ptrs(sl[l])
+            net.w_lo[l], net.wt_lo[l] = plan.mat_ptr(sl[l].lo), plan.mat_ptr(sl[l].lo_t)
+        net.w_feat, net.b_feat, net.wt_feat = plan.wb_ptrs(sl["feat"])
         net.n_layers, net.skip_layer, net.rb, net.multires, net.scale = Lm, skip, RB, self.multires, self.scale
         net.adj_mode = adj
-        plan.net = net
-        plan.slots = slots
-        plan.packed_version = None
-        self._plans[key] = plan
-        return plan
-
-    def _param_version(self):
-        # _ncw_version_srcs: base tensors whose in-place updates change these parameters without touching their
-        # own version counters (trainer.FlatParams re-seats p.data into one flat buffer)
-        return tuple(p._version for p in self.parameters()) + \
-            tuple(t._version for t in self.__dict__.get("_ncw_version_srcs", ()))
-
-    def packed(self, prec):
-        """Pack plan with weights up to date on the current stream."""
-        plan = self.plan(prec)
-        ver = (self._param_version(), plan.param_key())
-        if plan.packed_version != ver:
-            plan.pack()
-            plan.packed_version = (self._param_version(), plan.param_key())
+        plan.net, plan.slots = net, sl
         return plan
 
     # ---- reference API ----------------------------------------------------------------------
@@ -295,6 +254,18 @@ class SDFNetwork(nn.Module):
         return out.reshape(-1, 1)
 
     # ---- training path: forward with input gradient, backward, weight gradients ---------------------
+    def _stash_fields(self, train, h_lo):
+        RB, Lm = self.d_hidden // 32, self.n_lin
+        hid = {l: RB for l in range(1, Lm)}
+        # Softplus' is recomputed from h (s = 1 - exp(-100 h)): no stash vector of its own.  adj_mode 2 (W = 512): the slots hold the fp16
+        # RESIDUALS of h (NcwSdfStash.s = h_lo), written by the split value chain and read by the adjoint sweep of the same launch
+        s = hid if h_lo else {}
+        if not train:
+            return [("feat", RB), ("h", hid), ("s", s)]
+        return [("gamma", 2), ("feat", RB), ("dfeat", RB), ("zsdf", 1), ("one", 1), ("h", hid), ("s", s),
+                ("t", {l: RB for l in range(Lm - 1)}), ("qbar", {l: 2 if l == 0 else RB for l in range(Lm)}),
+                ("zbar", {l: RB for l in range(Lm - 1)})]
+
     def fwd_stash(self, pts, n, prec, train=True):
         """ncw_sdf_fwd: returns (sdf [n], grad [n,3], ctx).  ctx carries the activation stash.
         train=False: the forward-only render (validation / novel views / vertex colours: rendering/renderer.py:785-916 under
@@ -303,44 +274,9 @@ class SDFNetwork(nn.Module):
         of the training stash's 21 KB (NcwSdfStash.t[0] == NULL selects the kernels that store nothing else)."""
         dev = self.lin0.bias.device
         plan = self.packed(prec)
-        RB, Lm = self.d_hidden // 32, self.n_lin
         h_lo = int(plan.net.adj_mode) == 2  # the adjoint sweep takes phi' from h as an fp16 hi + lo pair (csrc/ncw_sdf16.hip)
-
-        def build_render():
-            ar = StashArena(dev, prec, n)
-            ids = dict(feat=ar.new(RB))
-            ids["h"] = {l: ar.new(RB) for l in range(1, Lm)}
-            ids["s"] = {l: ar.new(RB) for l in range(1, Lm)} if h_lo else {}
-            ar.allocate()
-            st = L.NcwSdfStash()
-            st.feat = ar.ptr(ids["feat"])
-            for l, i in ids["h"].items():
-                st.h[l] = ar.ptr(i)
-            for l, i in ids["s"].items():
-                st.s[l] = ar.ptr(i)
-            return dict(arena=ar, ids=ids, stash=st)
-
-        def build():
-            ar = StashArena(dev, prec, n)
-            ids = dict(gamma=ar.new(2), feat=ar.new(RB), dfeat=ar.new(RB), zsdf=ar.new(1), one=ar.new(1))
-            ids["h"] = {l: ar.new(RB) for l in range(1, Lm)}
-            # Softplus' is recomputed from h (s = 1 - exp(-100 h)): no stash vector of its own.  adj_mode 2 (W = 512): the slots hold the fp16
-            # RESIDUALS of h (NcwSdfStash.s = h_lo), written by the split value chain and read by the adjoint sweep of the same launch
-            ids["s"] = {l: ar.new(RB) for l in range(1, Lm)} if h_lo else {}
-            ids["t"] = {l: ar.new(RB) for l in range(Lm - 1)}
-            ids["qbar"] = {l: ar.new(2 if l == 0 else RB) for l in range(Lm)}
-            ids["zbar"] = {l: ar.new(RB) for l in range(Lm - 1)}
-            ar.allocate()
-            st = L.NcwSdfStash()
-            st.gamma, st.feat, st.dfeat = ar.ptr(ids["gamma"]), ar.ptr(ids["feat"]), ar.ptr(ids["dfeat"])
-            st.zsdf, st.one = ar.ptr(ids["zsdf"]), ar.ptr(ids["one"])
-            for k in ("h", "s", "t", "qbar", "zbar"):
-                for l, i in ids[k].items():
-                    getattr(st, k)[l] = ar.ptr(i)
-            return dict(arena=ar, ids=ids, stash=st)
-
-        ent = self.__dict__.setdefault("_stash_cache", StashCache()).acquire((prec, n, str(dev), h_lo, bool(train)),
-                                                                             build if train else build_render)
+        ent = self.__dict__.setdefault("_stash_cache", StashCache()).acquire(
+            (prec, n, str(dev), h_lo, bool(train)), lambda: build_stash(L.NcwSdfStash, self._stash_fields(train, h_lo), dev, prec, n))
         ar, ids, st = ent["arena"], ent["ids"], ent["stash"]
         sdf = torch.empty(n, device=dev, dtype=torch.float32)
         grad = torch.empty(n, 3, device=dev, dtype=torch.float32)
@@ -360,66 +296,24 @@ class SDFNetwork(nn.Module):
 
     def add_wgrads(self, ctx, batch):
         """Queue every weight-gradient product of the SDF net (forward + adjoint terms) on `batch`."""
-        plan, ar, ids = ctx["plan"], ctx["arena"], ctx["ids"]
+        plan, ar, ids, sl = ctx["plan"], ctx["arena"], ctx["ids"], ctx["plan"].slots
         RB, Lm = self.d_hidden // 32, self.n_lin
         skip = self.skip_in[0] if self.skip_in else -1
         P = ar.ptr
         for l in range(Lm - 1):
-            dn = plan.slots[l][3]
-            ld = plan.dense_ld(dn)
+            dp, ld, db = plan.dense_ptrs(sl[l])
             y_f, rby = (P(ids["gamma"]), 2) if l == 0 else (P(ids["h"][l]), RB)
-            batch.add(P(ids["zbar"][l]), RB, y_f, rby, plan.dense_ptr(dn), ld, plan.dense_bias_ptr(dn))
-            batch.add(P(ids["t"][l]), RB, P(ids["qbar"][l]), rby, plan.dense_ptr(dn), ld)
+            batch.add(P(ids["zbar"][l]), RB, y_f, rby, dp, ld, db)
+            batch.add(P(ids["t"][l]), RB, P(ids["qbar"][l]), rby, dp, ld)
             if l == skip:
                 off = 4 * 32 * RB
-                batch.add(P(ids["zbar"][l]), RB, P(ids["gamma"]), 2, plan.dense_ptr(dn) + off, ld)
-                batch.add(P(ids["t"][l]), RB, P(ids["qbar"][0]), 2, plan.dense_ptr(dn) + off, ld)
-        s = plan.slots[Lm - 1]
-        dn, dnf = s[3], s[7]
+                batch.add(P(ids["zbar"][l]), RB, P(ids["gamma"]), 2, dp + off, ld)
+                batch.add(P(ids["t"][l]), RB, P(ids["qbar"][0]), 2, dp + off, ld)
         hl = P(ids["h"][Lm - 1])
-        batch.add(P(ids["dfeat"]), RB, hl, RB, plan.dense_ptr(dnf), plan.dense_ld(dnf), plan.dense_bias_ptr(dnf))
-        batch.add(P(ids["zsdf"]), 1, hl, RB, plan.dense_ptr(dn), plan.dense_ld(dn), plan.dense_bias_ptr(dn))
-        batch.add(P(ids["one"]), 1, P(ids["qbar"][Lm - 1]), RB, plan.dense_ptr(dn), plan.dense_ld(dn))
-
-
-class _PackedNet(nn.Module):
-    """Shared plan/pack caching for the parameter-holder modules."""
-
-    def _init_plans(self):
-        self._plans = {}
-
-    def _plan_switches(self):
-        """Mutable attributes `_build_plan` reads (part of the plan cache key)."""
-        return ()
-
-    def _param_version(self):
-        # _ncw_version_srcs: base tensors whose in-place updates change these parameters without touching their
-        # own version counters (trainer.FlatParams re-seats p.data into one flat buffer)
-        return tuple(p._version for p in self.parameters()) + \
-            tuple(t._version for t in self.__dict__.get("_ncw_version_srcs", ()))
-
-    def _first_param(self):
-        return next(self.parameters())
-
-    def plan(self, prec):
-        dev = self._first_param().device
-        # switches read when the plan is BUILT (residual matrices present or not) belong to the key: flipping `.refine` /
-        # `.weight_split` after the first forward selects (or builds) the matching plan instead of being a silent no-op
-        key = (prec, str(dev)) + tuple(self._plan_switches())
-        p = self._plans.get(key)
-        if p is None:
-            p = self._build_plan(prec, dev)
-            p.packed_version = None
-            self._plans[key] = p
-        return p
-
-    def packed(self, prec):
-        plan = self.plan(prec)
-        ver = (self._param_version(), plan.param_key())
-        if plan.packed_version != ver:
-            plan.pack()
-            plan.packed_version = (self._param_version(), plan.param_key())
-        return plan
+        batch.add(P(ids["dfeat"]), RB, hl, RB, *plan.dense_ptrs(sl["feat"]))
+        dp, ld, db = plan.dense_ptrs(sl[Lm - 1])
+        batch.add(P(ids["zsdf"]), 1, hl, RB, dp, ld, db)
+        batch.add(P(ids["one"]), 1, P(ids["qbar"][Lm - 1]), RB, dp, ld)
 
 
 class RenderingNetwork(_PackedNet):
@@ -467,7 +361,7 @@ class RenderingNetwork(_PackedNet):
         self.act_split = None if env is None else (env not in ("0", ""))
         self._init_plans()
 
-    def _plan_switches(self):
+    def _plan_switches(self, prec):
         return (bool(self.weight_split), self.act_split)
 
     @property
@@ -483,93 +377,51 @@ class RenderingNetwork(_PackedNet):
 
         split = prec == L.PREC_F16 and self.weight_split  # forward matrices as fp16 hi + lo pairs (ncw_color_fwd)
 
-        def full(name, mod, rb_out, rb_in, segs):
-            v, g, b = _wvb(mod)
-            m, bs, mt = plan.new_matrix(rb_out, rb_in), plan.new_bias(rb_out), plan.new_matrix(rb_in, rb_out)
-            dn = plan.new_dense_grad(rb_out, rb_in)
-            plan.add_pack(v, g, b, m, bs, segs)
-            plan.add_pack(v, g, None, mt, None, segs, transpose=True)
-            plan.add_unpack(v, g, b, dn, segs)
-            lo = None
-            if split:
-                lo = plan.new_matrix(rb_out, rb_in)
-                plan.add_pack(v, g, None, lo, None, segs, residual=True)
-            sl[name] = (m, bs, mt, dn, lo)
-
-        full("f", self.xyz_encoding_final, RBF, RBF, [(0, W, 0)])
-        full("e0", self.static_encoding[0], RBH, RBF + 3, [(0, W, 0), (W, 27 + A, 32 * RBF)])
+        sl["f"] = plan.add_linear(self.xyz_encoding_final, RBF, RBF, [(0, W, 0)], lo=split)
+        sl["e0"] = plan.add_linear(self.static_encoding[0], RBH, RBF + 3, [(0, W, 0), (W, 27 + A, 32 * RBF)], lo=split)
         for i in range(1, self.n_head):
-            full("e%d" % i, self.static_encoding[i], RBH, RBH, [(0, HC, 0)])
-        full("l0", self.lin0, RBC, RBH + 1, [(6, HC, 0), (0, 6, 32 * RBH)])
+            sl["e%d" % i] = plan.add_linear(self.static_encoding[i], RBH, RBH, [(0, HC, 0)], lo=split)
+        sl["l0"] = plan.add_linear(self.lin0, RBC, RBH + 1, [(6, HC, 0), (0, 6, 32 * RBH)], lo=split)
         for l in range(1, self.n_lin - 1):
-            full("l%d" % l, getattr(self, "lin%d" % l), RBC, RBC, [(0, self.d_hidden, 0)])
-        full("l%d" % (self.n_lin - 1), getattr(self, "lin%d" % (self.n_lin - 1)), 1, RBC, [(0, self.d_hidden, 0)])
+            sl["l%d" % l] = plan.add_linear(getattr(self, "lin%d" % l), RBC, RBC, [(0, self.d_hidden, 0)], lo=split)
+        last = self.n_lin - 1
+        sl["l%d" % last] = plan.add_linear(getattr(self, "lin%d" % last), 1, RBC, [(0, self.d_hidden, 0)], lo=split)
         plan.finalize()
-        net.w_f, net.b_f, net.wt_f = plan.mat_ptr(sl["f"][0]), plan.bias_ptr(sl["f"][1]), plan.mat_ptr(sl["f"][2])
-        net.w_f_lo = plan.mat_ptr(sl["f"][4]) if split else None
+        net.w_f, net.b_f, net.wt_f = plan.wb_ptrs(sl["f"])
+        net.w_f_lo = plan.mat_ptr(sl["f"].lo)
         for i in range(self.n_head):
             s = sl["e%d" % i]
-            net.w_e[i], net.b_e[i], net.wt_e[i] = plan.mat_ptr(s[0]), plan.bias_ptr(s[1]), plan.mat_ptr(s[2])
-            net.w_e_lo[i] = plan.mat_ptr(s[4]) if split else None
+            net.w_e[i], net.b_e[i], net.wt_e[i] = plan.wb_ptrs(s)
+            net.w_e_lo[i] = plan.mat_ptr(s.lo)
         for l in range(self.n_lin):
             s = sl["l%d" % l]
-            net.w_l[l], net.b_l[l], net.wt_l[l] = plan.mat_ptr(s[0]), plan.bias_ptr(s[1]), plan.mat_ptr(s[2])
-            net.w_l_lo[l] = plan.mat_ptr(s[4]) if split else None
+            net.w_l[l], net.b_l[l], net.wt_l[l] = plan.wb_ptrs(s)
+            net.w_l_lo[l] = plan.mat_ptr(s.lo)
         net.n_head, net.n_lin, net.rbf, net.rbh, net.rbc, net.n_a = self.n_head, self.n_lin, RBF, RBH, RBC, A
         asplit = True if self.act_split is None else bool(self.act_split)
         net.act_split = 1 if (split and asplit and (RBF, RBH, RBC) in ((8, 4, 8), (16, 4, 8))) else 0
         plan.net, plan.slots = net, sl
         return plan
 
+    def _stash_fields(self, train):
+        RBF, RBH, RBC = self.d_feature // 32, self.head_channels // 32, self.d_hidden // 32
+        if not train:
+            return []
+        return [("aux1", 3), ("aux2", 1), ("f", RBF), ("zf", RBF), ("zo", 1), ("e", [RBH] * self.n_head),
+                ("ze", [RBH] * self.n_head), ("x", [RBC] * (self.n_lin - 1)), ("zx", [RBC] * (self.n_lin - 1))]
+
     def fwd_stash(self, pts, n, prec, normals, a, feat_ptr, train=True):
         """train=False: the forward-only render -- NOTHING is stashed (NcwColorStash.aux1 == NULL selects color_render_kernel);
         the same rgb bit for bit."""
         dev = self._first_param().device
         plan = self.packed(prec)
-        RBF, RBH, RBC = self.d_feature // 32, self.head_channels // 32, self.d_hidden // 32
-
-        def build_render():
-            return dict(arena=StashArena(dev, prec, n).allocate(), ids={}, stash=L.NcwColorStash())
-
-        def build():
-            ar = StashArena(dev, prec, n)
-            ids = dict(aux1=ar.new(3), aux2=ar.new(1), f=ar.new(RBF), zf=ar.new(RBF), zo=ar.new(1))
-            ids["e"] = [ar.new(RBH) for _ in range(self.n_head)]
-            ids["ze"] = [ar.new(RBH) for _ in range(self.n_head)]
-            ids["x"] = [ar.new(RBC) for _ in range(self.n_lin - 1)]
-            ids["zx"] = [ar.new(RBC) for _ in range(self.n_lin - 1)]
-            ar.allocate()
-            st = L.NcwColorStash()
-            for k in ("aux1", "aux2", "f", "zf", "zo"):
-                setattr(st, k, ar.ptr(ids[k]))
-            for k in ("e", "ze", "x", "zx"):
-                for i, v in enumerate(ids[k]):
-                    getattr(st, k)[i] = ar.ptr(v)
-            return dict(arena=ar, ids=ids, stash=st)
-
-        ent = self.__dict__.setdefault("_stash_cache", StashCache()).acquire((prec, n, str(dev), bool(train)),
-                                                                             build if train else build_render)
+        ent = self.__dict__.setdefault("_stash_cache", StashCache()).acquire(
+            (prec, n, str(dev), bool(train)), lambda: build_stash(L.NcwColorStash, self._stash_fields(train), dev, prec, n))
         ar, ids, st = ent["arena"], ent["ids"], ent["stash"]
         rgb = torch.empty(n, 3, device=dev, dtype=torch.float32)
         normals = normals.contiguous().float()
         a = a.contiguous().float()
-        # 16-bit modes: the per-RAY part of the head's first layer -- W_e0[:, view-dir | appearance columns] . [gamma_4(d) | a]
-        # (models/neuconw.py:131-140) -- is evaluated once per ray in fp32 (ncw_aux_ray_bias) and added to that layer's bias;
-        # rounding `a` and gamma(d) to 16 bits is coherent along a ray and was the largest term of the fp16 mode's colour
-        # error on trained weights (scripts/diag/emul_color16.py).  The backward / weight gradients are unchanged.
-        st.aux_bias = None
-        lin0 = self.static_encoding[0]
-        if prec != L.PREC_F32 and self.ray_bias and pts.rays_d and not hasattr(lin0, "weight_v"):
-            R, no = a.shape[0], 32 * RBH
-            ab = ent.get("aux_bias")
-            if ab is None or ab.shape[0] != R:
-                ab = ent["aux_bias"] = torch.empty(R, no, device=dev, dtype=torch.float32)
-            w0 = lin0.weight.detach()
-            assert w0.is_contiguous() and w0.dtype == torch.float32 and w0.shape == (self.head_channels, self.d_feature + 27 + self.n_a)
-            L.check(L.get_lib().ncw_aux_ray_bias(L.ptr(w0), w0.shape[1], self.d_feature, self.head_channels,
-                                                 ctypes.c_void_p(pts.rays_d), L.ptr(a), self.n_a, R, L.ptr(ab), no, L.stream_ptr(dev)),
-                    "ncw_aux_ray_bias")
-            st.aux_bias = ab.data_ptr()
+        ray_head_bias(st, ent, self.static_encoding[0], self.ray_bias, prec, pts, a, self.d_feature, self.head_channels, self.n_a)
         L.check(L.get_lib().ncw_color_fwd(plan.net, prec, pts, n, L.ptr(normals), L.ptr(a), feat_ptr, L.ptr(rgb), st,
                                           L.stream_ptr(dev)), "ncw_color_fwd")
         return rgb, dict(arena=ar, ids=ids, stash=st, pts=pts, n=n, prec=prec, plan=plan, rgb=rgb, feat_ptr=feat_ptr,
@@ -592,25 +444,21 @@ class RenderingNetwork(_PackedNet):
         RBF, RBH, RBC = self.d_feature // 32, self.head_channels // 32, self.d_hidden // 32
         P = ar.ptr
 
-        def dn(name):
-            d = sl[name][3]
-            return plan.dense_ptr(d), plan.dense_ld(d), plan.dense_bias_ptr(d)
-
-        dp, ld, db = dn("f")
+        dp, ld, db = plan.dense_ptrs(sl["f"])
         batch.add(P(ids["zf"]), RBF, ctx["feat_ptr"], RBF, dp, ld, db)
-        dp, ld, db = dn("e0")
+        dp, ld, db = plan.dense_ptrs(sl["e0"])
         batch.add(P(ids["ze"][0]), RBH, P(ids["f"]), RBF, dp, ld, db)
         batch.add(P(ids["ze"][0]), RBH, P(ids["aux1"]), 3, dp + 4 * 32 * RBF, ld)
         for i in range(1, self.n_head):
-            dp, ld, db = dn("e%d" % i)
+            dp, ld, db = plan.dense_ptrs(sl["e%d" % i])
             batch.add(P(ids["ze"][i]), RBH, P(ids["e"][i - 1]), RBH, dp, ld, db)
-        dp, ld, db = dn("l0")
+        dp, ld, db = plan.dense_ptrs(sl["l0"])
         batch.add(P(ids["zx"][0]), RBC, P(ids["e"][self.n_head - 1]), RBH, dp, ld, db)
         batch.add(P(ids["zx"][0]), RBC, P(ids["aux2"]), 1, dp + 4 * 32 * RBH, ld)
         for l in range(1, self.n_lin - 1):
-            dp, ld, db = dn("l%d" % l)
+            dp, ld, db = plan.dense_ptrs(sl["l%d" % l])
             batch.add(P(ids["zx"][l]), RBC, P(ids["x"][l - 1]), RBC, dp, ld, db)
-        dp, ld, db = dn("l%d" % (self.n_lin - 1))
+        dp, ld, db = plan.dense_ptrs(sl["l%d" % (self.n_lin - 1)])
         batch.add(P(ids["zo"]), 1, P(ids["x"][self.n_lin - 2]), RBC, dp, ld, db)
 
 

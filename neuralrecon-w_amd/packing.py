@@ -7,13 +7,33 @@ A plan owns (per precision)
 Padding is written once (zeros) and never touched again.
 """
 
+from typing import NamedTuple, Optional
+
 import torch
+from torch import nn
 
 from . import lib as L
 
 
 def _elem_size(prec):
     return 4 if prec == L.PREC_F32 else 2
+
+
+def _wvb(m):
+    """(weight-or-v, g-or-None, bias) of a WNLinear / PlainLinear / nn.Linear."""
+    if hasattr(m, "weight_v"):
+        return m.weight_v, m.weight_g, m.bias
+    return m.weight, None, m.bias
+
+
+class LinearSlot(NamedTuple):
+    """Where PackPlan.add_linear put one Linear (or a row range of one): indices into the plan's arenas."""
+    mat: int                    # packed matrix (forward orientation)
+    bias: int
+    mat_t: int                  # packed transposed matrix (the backward's operand)
+    dense: int                  # dense f32 gradient matrix (+ bias gradient)
+    lo: Optional[int] = None    # residual of `mat` (the low half of an fp16 hi + lo pair)
+    lo_t: Optional[int] = None  # residual of `mat_t`
 
 
 class PackPlan:
@@ -71,6 +91,30 @@ class PackPlan:
         self._unpack.append(dict(weight=weight, g=g, bias=bias, dense=dense, segs=list(segs), row0=row0,
                                  nrows=nrows, drow0=drow0, scale=float(scale)))
 
+    def add_linear(self, mod, rb_out, rb_in, segs, scale=1.0, row0=0, nrows=None, lo=False, lo_t=False):
+        """Rows [row0, row0 + nrows) of the Linear `mod` (WNLinear / PlainLinear / nn.Linear): its packed matrix, bias,
+        transposed matrix and dense gradient, with their pack / unpack descriptors, then (lo / lo_t) the residual matrices."""
+        v, g, b = _wvb(mod)
+        m, bs, mt = self.new_matrix(rb_out, rb_in), self.new_bias(rb_out), self.new_matrix(rb_in, rb_out)
+        dn = self.new_dense_grad(rb_out, rb_in)
+        self.add_pack(v, g, b, m, bs, segs, row0=row0, nrows=nrows, scale=scale)
+        self.add_pack(v, g, None, mt, None, segs, row0=row0, nrows=nrows, transpose=True, scale=scale)
+        self.add_unpack(v, g, b, dn, segs, row0=row0, nrows=nrows, scale=scale)
+        return self.add_residuals(mod, LinearSlot(m, bs, mt, dn), segs, scale, row0, nrows, lo, lo_t)
+
+    def add_residuals(self, mod, slot, segs, scale=1.0, row0=0, nrows=None, lo=False, lo_t=False):
+        """The residual matrices of a slot (add_linear's last step; on its own where a Linear is split over two slots and the
+        residuals come after both) -> the slot with `lo` / `lo_t` filled in."""
+        v, g, _ = _wvb(mod)
+        _, rb_out, rb_in = self._mats[slot.mat]
+        if lo:
+            slot = slot._replace(lo=self.new_matrix(rb_out, rb_in))
+            self.add_pack(v, g, None, slot.lo, None, segs, row0=row0, nrows=nrows, scale=scale, residual=True)
+        if lo_t:
+            slot = slot._replace(lo_t=self.new_matrix(rb_in, rb_out))
+            self.add_pack(v, g, None, slot.lo_t, None, segs, row0=row0, nrows=nrows, transpose=True, scale=scale, residual=True)
+        return slot
+
     # ---- finalisation ---------------------------------------------------------------------
     def finalize(self):
         dev = self.device
@@ -82,7 +126,8 @@ class PackPlan:
         return self
 
     def mat_ptr(self, mat):
-        return self.w_arena.data_ptr() + self._mats[mat][0]
+        """None (a residual the slot does not have) -> None: a NULL pointer in the net structs."""
+        return None if mat is None else self.w_arena.data_ptr() + self._mats[mat][0]
 
     def bias_ptr(self, slot):
         return self.b_arena.data_ptr() + 4 * self._biases[slot][0]
@@ -100,6 +145,14 @@ class PackPlan:
 
     def dense_ld(self, d):
         return self._dense[d][2]
+
+    def wb_ptrs(self, slot):
+        """(w, b, wt) device pointers of a slot, as the net structs take them."""
+        return self.mat_ptr(slot.mat), self.bias_ptr(slot.bias), self.mat_ptr(slot.mat_t)
+
+    def dense_ptrs(self, slot):
+        """(dense gradient, its leading dimension, bias gradient) of a slot, as WgradBatch.add takes them."""
+        return self.dense_ptr(slot.dense), self.dense_ld(slot.dense), self.dense_bias_ptr(slot.dense)
 
     def param_key(self):
         return tuple(p["weight"].data_ptr() for p in self._pack)
@@ -206,6 +259,47 @@ class PackPlan:
         L.check(lib.ncw_unpack_grads(L.ptr(tab), L.ptr(pre), len(descs), prefix[-1], L.stream_ptr(self.device)),
                 "ncw_unpack_grads")
         return tab, pre  # keep alive until the stream has consumed them
+
+
+class _PackedNet(nn.Module):
+    """Shared plan/pack caching for the parameter-holder modules."""
+
+    def _init_plans(self):
+        self._plans = {}
+
+    def _plan_switches(self, prec):
+        """Mutable attributes `_build_plan` reads (part of the plan cache key)."""
+        return ()
+
+    def _param_version(self):
+        # _ncw_version_srcs: base tensors whose in-place updates change these parameters without touching their
+        # own version counters (trainer.FlatParams re-seats p.data into one flat buffer)
+        return tuple(p._version for p in self.parameters()) + \
+            tuple(t._version for t in self.__dict__.get("_ncw_version_srcs", ()))
+
+    def _first_param(self):
+        return next(self.parameters())
+
+    def plan(self, prec):
+        dev = self._first_param().device
+        # switches read when the plan is BUILT (residual matrices present or not) belong to the key: flipping `.refine` /
+        # `.weight_split` / `.adj_split` after the first forward selects (or builds) the matching plan instead of being a silent no-op
+        key = (prec, str(dev)) + tuple(self._plan_switches(prec))
+        p = self._plans.get(key)
+        if p is None:
+            p = self._build_plan(prec, dev)
+            p.packed_version = None
+            self._plans[key] = p
+        return p
+
+    def packed(self, prec):
+        """Pack plan with weights up to date on the current stream."""
+        plan = self.plan(prec)
+        ver = (self._param_version(), plan.param_key())
+        if plan.packed_version != ver:
+            plan.pack()
+            plan.packed_version = (self._param_version(), plan.param_key())
+        return plan
 
 
 # ---- several plans in ONE launch ------------------------------------------------------------------------------------

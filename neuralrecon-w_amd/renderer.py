@@ -55,7 +55,7 @@ class _RenderFn(torch.autograd.Function):
             # evaluates the NeRF on all S + O samples all the same.  Identical outputs and gradients; bg_dense=True
             # evaluates everything like the reference.  (Columns are paired with primary samples by index, as there.)
             select = refine = None
-            if rdr.trim_sphere and nerf.supports_selection(prec):
+            if rdr.trim_sphere:
                 refine = (z, M - S)  # fp16 mode: the samples the compositor can use are re-evaluated in split precision (ncw_nerf_refine)
                 if not rdr.bg_dense:
                     select = refine

@@ -1,6 +1,7 @@
 """Activation-stash arenas and batched weight-gradient launches (host side)."""
 
 import os
+from typing import NamedTuple
 
 import torch
 
@@ -55,6 +56,42 @@ class StashArena:
                                                 self.ptr(i), L.stream_ptr(self.device)), "ncw_stash_from_rows")
 
 
+def build_stash(struct_type, fields, device, prec, n_points):
+    """A StashCache entry -- dict(arena=, ids=, stash=) -- of one network's activation stash: carves an arena in the order of
+    `fields`, allocates it and points the `struct_type` instance (an Ncw*Stash) at it.  fields: [(name, rb)] for a single
+    vector, [(name, {layer: rb})] or [(name, [rb, ...])] for the struct's per-layer pointer arrays; `ids` keeps those shapes."""
+    ar = StashArena(device, prec, n_points)
+    ids = {}
+    for name, rb in fields:
+        if isinstance(rb, dict):
+            ids[name] = {l: ar.new(r) for l, r in rb.items()}
+        else:
+            ids[name] = [ar.new(r) for r in rb] if isinstance(rb, list) else ar.new(rb)
+    ar.allocate()
+    st = struct_type()
+    for name, i in ids.items():
+        if isinstance(i, int):
+            setattr(st, name, ar.ptr(i))
+        else:
+            for l, v in (i.items() if isinstance(i, dict) else enumerate(i)):
+                getattr(st, name)[l] = ar.ptr(v)
+    return dict(arena=ar, ids=ids, stash=st)
+
+
+class WgradProduct(NamedTuple):
+    """One product of a WgradBatch: the operands of an NcwWgradDesc and the points it covers."""
+    x: int
+    rbx: int
+    y: int
+    rby: int
+    dense: int
+    ld: int
+    dbias: int
+    n: int
+    n_dev: int   # device int32[1] address of the selection's count, or 0: all n points
+    frac: float  # share of n the selection is expected to hold (1.0 without one)
+
+
 class WgradBatch:
     """Collects (X, Y, dense) weight-gradient products and runs them in one launch.
 
@@ -80,8 +117,8 @@ class WgradBatch:
         self.items = []
 
     def add(self, x_ptr, rbx, y_ptr, rby, dense_ptr, ld, dbias_ptr=0, n=None):
-        self.items.append((x_ptr, rbx, y_ptr, rby, dense_ptr, ld, dbias_ptr, self.n if n is None else int(n), self.n_dev,
-                           self.sel_fraction if self.n_dev else 1.0))
+        self.items.append(WgradProduct(x_ptr, rbx, y_ptr, rby, dense_ptr, ld, dbias_ptr, self.n if n is None else int(n),
+                                       self.n_dev, self.sel_fraction if self.n_dev else 1.0))
 
     def extend(self, other):
         """Take over another batch's products (they keep their own point count)."""
@@ -94,7 +131,7 @@ class WgradBatch:
     @staticmethod
     def algorithmic_bytes(items, elem=2):
         """Stash bytes the products stream from HBM: every X and Y block once per product."""
-        return sum((it[1] + it[3]) * 1024 * elem * ((it[7] + 31) // 32) for it in items)
+        return sum((it.rbx + it.rby) * 1024 * elem * ((it.n + 31) // 32) for it in items)
 
     def _table(self, items, tile, ksplits, ksplit, n):
         key = (tuple(items), tuple(ksplits), self.prec, tile, ksplit, n, str(self.device))
@@ -102,15 +139,15 @@ class WgradBatch:
         if hit is None:
             xb, yb = (4, 4) if tile is None else ((4, 8) if tile == 0 else (8, 8))
             descs, prefix = [], [0]
-            for (x, rbx, y, rby, dense, ld, db, ni, ndev, _frac), ksp in zip(items, ksplits):
+            for it, ksp in zip(items, ksplits):
                 d = L.NcwWgradDesc()
-                d.x, d.y, d.dense, d.dbias = x, y, dense, db
-                d.rbx, d.rby, d.ld = rbx, rby, ld
-                d.ksplit, d.n_points = (ksp, ni) if tile is not None else (0, 0)
-                if ndev:
-                    d.n_points_dev = ndev
+                d.x, d.y, d.dense, d.dbias = it.x, it.y, it.dense, it.dbias
+                d.rbx, d.rby, d.ld = it.rbx, it.rby, it.ld
+                d.ksplit, d.n_points = (ksp, it.n) if tile is not None else (0, 0)
+                if it.n_dev:
+                    d.n_points_dev = it.n_dev
                 descs.append(d)
-                prefix.append(prefix[-1] + ((rbx + xb - 1) // xb) * ((rby + yb - 1) // yb) * ksp)
+                prefix.append(prefix[-1] + ((it.rbx + xb - 1) // xb) * ((it.rby + yb - 1) // yb) * ksp)
             arr = (L.NcwWgradDesc * len(descs))(*descs)
             tab = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.device)
             pre = torch.tensor(prefix, dtype=torch.int32, device=self.device)
@@ -120,33 +157,33 @@ class WgradBatch:
         return (tile,) + hit
 
     def _plan(self):
-        items = [it for it in self.items if it[7] > 0]
+        items = [it for it in self.items if it.n > 0]
         if not items:
             return []
         if self.prec != L.PREC_F32:
             # cost of one (product, 256x256 quad): stash blocks streamed x tiles
             def quads(it):
-                return ((it[1] + 7) // 8) * ((it[3] + 7) // 8)
+                return ((it.rbx + 7) // 8) * ((it.rby + 7) // 8)
             def cost(it):
                 # a quad costs the same whatever its real block count (missing blocks are re-reads of a
                 # valid one, L2 hits): weighting by HBM bytes instead measured 1.55 ms vs 1.02 ms per step
-                tiles = (it[7] + 31) // 32
+                tiles = (it.n + 31) // 32
                 # a product sized on the device (dead-background elimination) is planned at the selection's EXPECTED share of
-                # its stash (it[9]: observed by the renderer, stash.SelectionProbe): the split only balances the launch, the
+                # its stash (it.frac: observed by the renderer, stash.SelectionProbe): the split only balances the launch, the
                 # kernel clamps to the real count.  (Round 5: a fixed 12.5 % under-planned the shipped 8 + 16 shape -- 18 % of
                 # its samples are selected -- whose 17 single-workgroup background products then ran 1.5x longer than the rest:
                 # weight-gradient launch 0.87 ms dense, 1.09 ms with the elimination; NOTEBOOK R5.4.)
-                return max(1, int(tiles * it[9] + 0.999)) if it[8] else tiles
+                return max(1, int(tiles * it.frac + 0.999)) if it.n_dev else tiles
             total = sum(cost(it) * quads(it) for it in items)
             per_wg = max(1.0, total / self.TARGET_WGS)
             ksplits = []
             for it in items:
-                tiles = (it[7] + 31) // 32
+                tiles = (it.n + 31) // 32
                 ksplits.append(int(max(1, min(tiles // 8 if tiles >= 8 else 1, round(cost(it) / per_wg)))))
-            return [self._table(items, 1, ksplits, 1, max(it[7] for it in items))]
+            return [self._table(items, 1, ksplits, 1, max(it.n for it in items))]
         groups = []
-        for n in sorted({it[7] for it in items}):
-            sub = [it for it in items if it[7] == n]
+        for n in sorted({it.n for it in items}):
+            sub = [it for it in items if it.n == n]
             ksplit = max(1, min(16, ((n + 31) // 32) // 8))
             groups.append(self._table(sub, None, [ksplit] * len(sub), ksplit, n))
         return groups

@@ -124,24 +124,60 @@ def test_no_cpu_fallback():
         rdr.render(torch.zeros(4, 10), torch.zeros(4, dtype=torch.long), torch.zeros(4, dtype=torch.long))
 
 
+def _lo_pairs(net):
+    """[(hi pointer, lo pointer, transposed)] of every residual field (`*_lo`) of a net struct with its hi field."""
+    out = []
+    for name, _ in net._fields_:
+        if name.endswith("_lo"):
+            hi, lo = getattr(net, name[:-3]), getattr(net, name)
+            pairs = zip(hi, lo) if hasattr(lo, "__len__") else [(hi, lo)]
+            out += [(h, l, name.startswith("wt")) for h, l in pairs]
+    return out
+
+
 def test_pack_plan_descriptors_cover_every_parameter():
-    """Host logic of the pack plan: every Linear of the three networks is packed (forward +
-    transposed) and has exactly one gradient-unpack descriptor per source row."""
+    """Host logic of the pack plan, at every SDF width and precision: every Linear of the three networks is packed
+    (forward + transposed) and has exactly one gradient-unpack descriptor per source row; every residual matrix a net struct
+    points at (`*_lo`: the low halves of the fp16 hi + lo pairs) is packed by exactly one `residual` descriptor over the same
+    rows / segments / orientation as its hi matrix, and the structs hold the residuals exactly where the split is on
+    (fp16 only; SDF: W = 256 / 512, every layer forward, transposed too; colour: every layer forward; background: width 256)."""
     from neuralrecon_w_amd import lib as L
     from tests._build import build_system
 
-    emb, neuconw, nerf, _ = build_system(device="cpu")
-    for mod in (neuconw.sdf_net, neuconw.color_net, nerf):
-        plan = mod.plan(L.PREC_BF16)
-        packed = {p["weight"].data_ptr() for p in plan._pack}
-        rows = {}
-        for u in plan._unpack:
-            rows.setdefault(u["weight"].data_ptr(), 0)
-            rows[u["weight"].data_ptr()] += u["nrows"]
-        for name, p in mod.named_parameters():
-            if p.dim() == 2 and not name.startswith("views_linears") and not name.endswith("weight_g"):
-                assert p.data_ptr() in packed, name
-                assert rows[p.data_ptr()] == p.shape[0], name
+    for W in (64, 256, 512):
+        kw = {} if W == 64 else dict(color_hidden=256, head=128, nerf_w=256)
+        emb, neuconw, nerf, _ = build_system(W=W, device="cpu", **kw)
+        for prec in (L.PREC_F32, L.PREC_BF16, L.PREC_F16):
+            for tag, mod in (("sdf", neuconw.sdf_net), ("color", neuconw.color_net), ("nerf", nerf)):
+                plan = mod.plan(prec)
+                packed = {p["weight"].data_ptr() for p in plan._pack}
+                rows = {}
+                for u in plan._unpack:
+                    rows.setdefault(u["weight"].data_ptr(), 0)
+                    rows[u["weight"].data_ptr()] += u["nrows"]
+                for name, p in mod.named_parameters():
+                    if p.dim() == 2 and not name.startswith("views_linears") and not name.endswith("weight_g"):
+                        assert p.data_ptr() in packed, name
+                        assert rows[p.data_ptr()] == p.shape[0], name
+                by_ptr = {}
+                for p in plan._pack:
+                    by_ptr.setdefault(plan.mat_ptr(p["mat"]), []).append(p)
+                pairs = _lo_pairs(plan.net)
+                for hi, lo, transposed in pairs:
+                    if lo:
+                        assert hi and len(by_ptr[lo]) == 1 and len(by_ptr[hi]) == 1, (tag, prec)
+                        d_lo, d_hi = by_ptr[lo][0], by_ptr[hi][0]
+                        assert d_lo["residual"] and not d_hi["residual"] and d_lo["transpose"] == d_hi["transpose"] == transposed
+                        assert d_lo["weight"] is d_hi["weight"] and d_lo["g"] is d_hi["g"] and d_lo["scale"] == d_hi["scale"]
+                        assert (d_lo["row0"], d_lo["nrows"], d_lo["segs"]) == (d_hi["row0"], d_hi["nrows"], d_hi["segs"])
+                        assert plan._mats[d_lo["mat"]][1:] == plan._mats[d_hi["mat"]][1:]
+                n_res = sum(1 for p in plan._pack if p["residual"])
+                assert n_res == sum(1 for _, lo, _ in pairs if lo), (tag, prec)  # no residual matrix that no struct field reads
+                fwd = sum(1 for h, lo, t in pairs if lo and not t)
+                bwd = sum(1 for h, lo, t in pairs if lo and t)
+                n_mod = sum(1 for h, _, t in pairs if h and not t)  # Linears of the network (the SDF feature rows have no `_lo` field)
+                split = prec == L.PREC_F16 and (tag == "color" or W in (256, 512))
+                assert (fwd, bwd) == ((n_mod, n_mod if tag == "sdf" else 0) if split else (0, 0)), (tag, prec, fwd, bwd)
 
 
 def test_same_seed_same_init_as_reference():

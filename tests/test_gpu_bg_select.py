@@ -141,7 +141,7 @@ def test_elimination_under_graph_capture():
         emb, neuconw, nerf, rdr = build_system(W=256, n_a=48, n_vocab=64, nerf_w=256, color_hidden=256, head=128, seed=6,
                                                prec=nw.PREC_F16, n_samples=16, n_importance=16)
         rdr.sync_free = True
-        assert nerf.supports_selection(nw.PREC_F16) and not rdr.bg_dense
+        assert not rdr.bg_dense
         train = nw.TrainStep(rdr, [emb, neuconw, nerf], loss_from_outputs, lr=1e-3, eps=1e-7, clip=0.99, capture=capture,
                              capture_warmup=3)
         curves.append([float(train(rays, ts, label, rgbs, background_rgb=bg, cos_anneal_ratio=0.1 * i, perturb_overwrite=0)[0])
