@@ -381,9 +381,11 @@ typedef struct NcwWgradDesc {
     int32_t rbx, rby, ld;
     int32_t ksplit;    /* ncw_wgrad_tiled only: > 0 overrides the launch-wide split-K for this product */
     int64_t n_points;  /* ncw_wgrad_tiled only: > 0 overrides the launch-wide point count            */
-    const int32_t* n_points_dev; /* ncw_wgrad_tiled only: DEVICE int32[1] or NULL; the product covers the first
-                                  * min(n_points, *n_points_dev) points of its stashes (a selection made on the
-                                  * device, NcwPoints mode 4); the K-slices re-divide that count */
+    const int32_t* n_points_dev; /* every entry point: DEVICE int32[1] or NULL (a selection made on the device, NcwPoints
+                                  * mode 4).  The kernels work in whole tiles of 32 points: the product covers the tiles
+                                  * [0, ceil(min(n_points, *n_points_dev) / 32)) of its stashes, all 32 lanes of the last one
+                                  * included, so X must be ZERO in the padded lanes of that tile (the producers write their
+                                  * cotangents there as zero; Y may hold anything finite); the K-slices re-divide those tiles */
 } NcwWgradDesc;
 /* descs: DEVICE array; wg_prefix: device int32[n_desc+1] exclusive prefix of
  * ceil(rbx/4)*ceil(rby/4)*ksplit workgroups per product; total_wgs = wg_prefix[n_desc]. */
