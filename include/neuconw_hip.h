@@ -685,6 +685,57 @@ int ncw_raster_backproject(const float* depth, const int64_t* pix, int64_t n, in
                            void* stream);
 int ncw_raster_mark(const float* dist, const int64_t* idx, int64_t n, float thr, int64_t m, uint8_t* flags, void* stream);
 
+
+/* ------------------------------------------------------------------------------------------
+ * Camera views (csrc/ncw_view.hip): what surrounds the forward-only render of one whole view in the reference's validation step
+ * (lightning_modules/neuconw_system.py:404-464, 533-546) -- ray generation, assembly of the chunk outputs into image planes, the
+ * depth colour map and the image metrics -- on the device, without a host round trip per chunk.  Every reduction is two-stage
+ * and fixed-order (no float atomics): bitwise reproducible run to run.  Images are f32; pixels are row-major.
+ *   ncw_view_rays     : datasets/ray_utils.py:18-52 (get_ray_directions + get_rays) and datasets/phototourism.py:769-782 for the
+ *                       pixels [p0, p0 + n) of the view: rays[n][8] = o, d, near, far.  Pixel (row j, column i), INTEGER
+ *                       coordinates (no + 0.5): dir = ((i - cx) / fx, -(j - cy) / fy, -1), d = c2w[:, :3] dir normalised,
+ *                       o = c2w[:, 3].  cam is a HOST struct (c2w row-major 3x4, "right up back" axes).  rays must be 16-byte
+ *                       aligned (rows are written as two 16-byte stores); returns -1 otherwise, or for a range outside the view.
+ *   ncw_view_store    : neuconw_system.py:440-460: one chunk's color [n,3] / depth [n] / compositor normals [n,3]
+ *                       (NcwCompositeOut.normals = sum_s gradients weights) to pixel offset p0 of the planar color_img [3,n_pix],
+ *                       depth_img [n_pix], normal_img [3,n_pix]; the normal plane holds v / |v| / 2 + 0.5 (0 / 0 stays NaN, as
+ *                       there).  Any of the three inputs may be NULL (not written).
+ *   ncw_image_minmax  : utils/visualization.py:18-20: minmax[2] (device) = min, max of nan_to_num(x[n]) (NaN -> 0, +-inf ->
+ *                       +-FLT_MAX), n >= 1.  scratch: ncw_image_reduce_scratch_bytes() bytes.
+ *   ncw_depth_colormap: utils/visualization.py:21-24: index = uint8(255 * ((x - mi) / (ma - mi + 1e-8))) in f32 with IEEE
+ *                       division and truncation (NaN from inf / inf -> 0), looked up in lut [256][3] uint8 (RGB);
+ *                       out_f32 [3,n] = value / 255 (torchvision ToTensor), out_u8 [3,n], out_index [n]: each may be NULL.
+ *   ncw_image_sqerr   : metrics.py:5-14: sum_out[1] f32 = sum of (pred - gt)^2 and count_out[1] int64 = number of elements over
+ *                       n pixels of 3 channels ([n,3], or planar [3,n] with planar = 1), restricted to the pixels with
+ *                       mask[i] != 0 when mask (uint8 [n]) is not NULL.  mse = sum / count, psnr = -10 log10(mse).
+ *   ncw_image_ssim    : metrics.py:16-21 over kornia's ssim(pred, gt, window, 'mean'): separable Gaussian window (sigma 1.5,
+ *                       window in {3, 5, 7, 9, 11}), reflect padding of (window - 1) / 2, moments mu_x, mu_y, E[x^2], E[y^2],
+ *                       E[xy] per channel, C1 = 0.01^2, C2 = 0.03^2, map = (2 mu_x mu_y + C1)(2 s_xy + C2) / ((mu_x^2 + mu_y^2 +
+ *                       C1)(s_x^2 + s_y^2 + C2)); ssim_out[1] = mean over pixels and channels of clamp(map, -1, 1), which
+ *                       equals the reference's 1 - 2 mean(clamp((1 - map) / 2, 0, 1)).  pred / gt planar [channels, height,
+ *                       width]; scratch: ncw_image_ssim_scratch_floats(channels, height, width) floats.  Returns -2 when
+ *                       height or width <= (window - 1) / 2 (reflect padding is undefined there), -1 for a bad window.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct NcwViewCamera {
+    float fx, fy, cx, cy;
+    float c2w[12];
+    int32_t width, height;
+    float near, far;
+} NcwViewCamera;
+
+int ncw_view_rays(const NcwViewCamera* cam, int64_t p0, int64_t n, float* rays, void* stream);
+int ncw_view_store(const float* color, const float* depth, const float* normals, int64_t p0, int64_t n, int64_t n_pix,
+                   float* color_img, float* depth_img, float* normal_img, void* stream);
+int64_t ncw_image_reduce_scratch_bytes(void);
+int ncw_image_minmax(const float* x, int64_t n, void* scratch, float* minmax, void* stream);
+int ncw_depth_colormap(const float* depth, int64_t n, const float* minmax, const uint8_t* lut, float* out_f32, uint8_t* out_u8,
+                       uint8_t* out_index, void* stream);
+int ncw_image_sqerr(const float* pred, const float* gt, const uint8_t* mask, int64_t n, int planar, void* scratch, float* sum_out,
+                    int64_t* count_out, void* stream);
+int64_t ncw_image_ssim_scratch_floats(int channels, int height, int width);
+int ncw_image_ssim(const float* pred, const float* gt, int channels, int height, int width, int window, float* scratch,
+                   float* ssim_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -415,11 +415,12 @@ class NeuconWRenderer:
         return rayops.sort_merge(z_vals, new_z_vals, sdf, new_sdf)
 
     @torch.no_grad()
-    def sparse_sampler(self, rays_o, rays_d, near, far, perturb, _rand=None):
+    def sparse_sampler(self, rays_o, rays_d, near, far, perturb, _rand=None, far_override=None):
+        """far_override: None = `self.nerf_far_override`; True / False decide it for this call (views.render_view)."""
         dev = rays_o.device
         R = rays_o.shape[0]
         rays_o, rays_d = rays_o.contiguous().float(), rays_d.contiguous().float()
-        if self.nerf_far_override:
+        if self.nerf_far_override if far_override is None else far_override:
             if self.octree_data is None:
                 self.octree_data = self.get_octree(dev)
             near, far, _ = self.get_near_far_octree(self.octree_data, rays_o, rays_d, near, far)
@@ -515,6 +516,14 @@ class NeuconWRenderer:
     def render(self, rays, ts, label, perturb_overwrite=-1, background_rgb=None, cos_anneal_ratio=0.0, _rand=None, _z_override=None):
         """_rand / _z_override are test hooks: the sampler's uniforms, and primary sample depths [R, S] that replace the sampler's
         (parity of the MLPs + compositor at FIXED sample positions, bench.py `parity.fixed_z`)."""
+        return self._render_with_normals(rays, ts, label, perturb_overwrite, background_rgb, cos_anneal_ratio, _rand, _z_override)[0]
+
+    def _render_with_normals(self, rays, ts, label, perturb_overwrite=-1, background_rgb=None, cos_anneal_ratio=0.0, _rand=None,
+                             _z_override=None, sfm_depth_loss=True, far_override=None):
+        """render()'s dictionary and the compositor's per-ray normal sum_s gradients weights[:, :n_samples] [R, 3]
+        (NcwCompositeOut.normals: what neuconw_system.py:445-458 sums on the host for the validation panel; views.render_view).
+        sfm_depth_loss=False leaves that entry zero (its reference form selects rays on the host: a device->host sync per call);
+        far_override: see sparse_sampler.  The defaults are render()."""
         device = rays.device
         if not rays.is_cuda:
             raise L.NeuconwHipError("NeuconWRenderer.render: rays are not on a GPU; the hot path has no CPU fallback")
@@ -549,7 +558,7 @@ class NeuconWRenderer:
         else:  # fp32 / reproducible mode, or an unusual embedding: torch's own (deterministic) lookup + backward
             a_embedded = emb_a(ts)
         perturb = self.perturb if perturb_overwrite < 0 else perturb_overwrite
-        n_samples, z_vals, z_vals_outside, sample_dist = self.sparse_sampler(rays_o, rays_d, near, far, perturb, _rand)
+        n_samples, z_vals, z_vals_outside, sample_dist = self.sparse_sampler(rays_o, rays_d, near, far, perturb, _rand, far_override)
         if _z_override is not None:
             assert tuple(_z_override.shape) == tuple(z_vals.shape), (tuple(_z_override.shape), tuple(z_vals.shape))
             z_vals = _z_override.to(device=device, dtype=torch.float32).contiguous()
@@ -569,7 +578,7 @@ class NeuconWRenderer:
          dists, eik_den, inv_s, s_val, weights_max) = outs
         weights_sum = wsum.unsqueeze(-1)
         has_mask = self.mesh_mask_list is not None
-        dense_depth = bool(self.depth_loss and self.sync_free)
+        dense_depth = bool(self.depth_loss and self.sync_free and sfm_depth_loss)
         ids = tuple(_label_id(name) for name in self.mesh_mask_list) if has_mask else ()
         # gradient_error (renderer.py:763-765, batch-global scalar), mask_error (:869-877) and -- in sync-free mode --
         # sfm_depth_loss in one launch.  Sync-free sfm_depth_loss: the reference returns the SELECTED entries (a
@@ -580,7 +589,7 @@ class NeuconWRenderer:
         mask_error = me.unsqueeze(-1) if has_mask else torch.zeros_like(weights_sum)
         if dense_depth:
             sfm_depth_loss = sfm_dense
-        elif self.depth_loss and torch.sum(depth_weight > 0) > 0:  # renderer.py:892-897
+        elif sfm_depth_loss and self.depth_loss and torch.sum(depth_weight > 0) > 0:  # renderer.py:892-897
             sfm_depth_loss = (((depth - depth_gt) ** 2) * depth_weight)[depth_weight > 0]
         else:
             sfm_depth_loss = torch.zeros_like(depth)
@@ -591,7 +600,7 @@ class NeuconWRenderer:
             "gradient_error": gradient_error, "inside_sphere": inside,
             "depth": depth, "floor_normal_error": (zn := torch.zeros_like(normals)), "floor_y_error": zn,
             "sfm_depth_loss": sfm_depth_loss,
-        }
+        }, normals
 
     # ---- helpers used by NeuconWSystem / extract_mesh (renderer.py:947-961) ---------------------------
     def sdf(self, pts):

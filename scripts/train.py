@@ -14,7 +14,11 @@
   * LR_SCHEDULER none / cosine / steplr stepped per epoch like PL steps the reference's scheduler (config.lr_at_epoch);
   * --val_mesh_every N (opt-in): every N steps the meshes of the reference's validation_step (neuconw_system.py:466-530) --
     128^3 over the unit sphere and 256^3 over `eval_bbx_detail` -- go to <SAVE_DIR>/<exp_name>/meshes/, and when
-    <root_dir>/gt.ply exists rank 0 scores the detailed one at 0.1 (neuralrecon_w_amd.evalmesh).
+    <root_dir>/gt.ply exists rank 0 scores the detailed one at 0.1 (neuralrecon_w_amd.evalmesh);
+  * --val_every N (opt-in): every N steps rank 0 renders the validation view (the dataset's `val` item: first training image,
+    downscale >= 8; neuconw_system.py:404-464, 533-546) with the forward-only render, prints val/psnr and writes the
+    GT | prediction | depth | normal panel to <SAVE_DIR>/<exp_name>/val/<step:08d>.png (neuralrecon_w_amd.views).  It draws no
+    random numbers and touches no training state: the training stream computes what it computes without it.
 """
 import argparse
 import os
@@ -68,7 +72,22 @@ def validation_meshes(rdr, scene, root, save_dir, step, rank, log_detail_skip=Tr
     return met
 
 
-def main():
+def validation_view(rdr, cfg, view, save_dir, step, chunk):
+    """neuconw_system.py:404-464, 533-546 on rank 0: renders `view` = (camera, gt, image id) of views.scene_view, prints
+    val/psnr (+ ssim) and writes val/<step:08d>.png.  Returns the render_view dictionary."""
+    from neuralrecon_w_amd import views
+
+    cam, gt, image_id = view
+    out = views.render_view(rdr, cam, ts=image_id, chunk=chunk, gt=gt,
+                            nerf_far_override=bool(cfg["NEUCONW"]["NEAR_FAR_OVERRIDE"]))  # :407
+    path = os.path.join(save_dir, "val", "%08d.png" % step)
+    views.write_panel(path, gt, out["color"], out["depth_vis"], out["normal"])
+    print("[val] step %d: val/psnr %.4f  val/ssim %.4f  (image %d, %d x %d) -> %s"
+          % (step, float(out["psnr"]), float(out["ssim"]), image_id, cam.width, cam.height, path))
+    return out
+
+
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--cfg_path", required=True)
     ap.add_argument("--root_dir", default=None, help="overrides DATASET.ROOT_DIR")
@@ -83,7 +102,18 @@ def main():
     ap.add_argument("--val_mesh_every", type=int, default=0,
                     help="every N steps: validation meshes (128^3 + 256^3 eval_bbx_detail) and, with <root_dir>/gt.ply, "
                          "their F-score at 0.1 (0 = off)")
-    args = ap.parse_args()
+    ap.add_argument("--val_every", type=int, default=0,
+                    help="every N steps rank 0 renders the validation view, prints val/psnr and writes the GT | prediction | "
+                         "depth | normal panel to <SAVE_DIR>/<exp_name>/val/ (0 = off)")
+    ap.add_argument("--val_chunk", type=int, default=0, help="rays per render launch of --val_every (0 = views.DEFAULT_CHUNK)")
+    ap.add_argument("--val_sfm_path", default=None,
+                    help="COLMAP model of --val_every under <root_dir>/dense/ -- the one the ray cache was built from (default: the "
+                         "reference's per-scene choice, ../neuralsfm for brandenburg_gate and palacio_de_bellas_artes, else sparse)")
+    return ap
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if os.environ.get("NCW_TRAIN_ONE_GPU_TEST"):  # plumbing test: the ranks share GPU 0 (collectives over gloo)
@@ -170,6 +200,12 @@ def main():
     # writes last.ckpt below
     epoch, in_epoch, gen_state0 = first_epoch, skip, gen.get_state()
     val_logged = False  # the "no eval_bbx_detail" line is printed once
+    val_view = None
+    if args.val_every > 0 and rank == 0:  # the dataset's `val` item, read once (data.py:80: no scene origin -> SfM percentiles)
+        from neuralrecon_w_amd import views
+
+        cam_, gt_, id_ = views.scene_view(root, img_downscale=int(pt["IMG_DOWNSCALE"]), split="val", sfm_path=args.val_sfm_path)
+        val_view = (cam_, gt_.to(dev), id_)
     for epoch in range(first_epoch, args.num_epochs):
         if hasattr(step_fn.opt, "lr"):  # utils/__init__.py:45-61: the scheduler steps once per epoch
             step_fn.opt.lr = C.lr_at_epoch(cfg, lr, epoch, args.num_epochs)
@@ -200,6 +236,8 @@ def main():
             if args.val_mesh_every > 0 and step % args.val_mesh_every == 0:  # neuconw_system.py:466-530
                 validation_meshes(rdr, scene, root, save_dir, step, rank, log_detail_skip=not val_logged)
                 val_logged = True
+            if val_view is not None and step % args.val_every == 0:  # neuconw_system.py:404-464, 533-546 (rank 0)
+                validation_view(rdr, cfg, val_view, save_dir, step, args.val_chunk or views.DEFAULT_CHUNK)
             if args.max_steps and step >= args.max_steps:
                 done = True
                 break
