@@ -736,6 +736,49 @@ int64_t ncw_image_ssim_scratch_floats(int channels, int height, int width);
 int ncw_image_ssim(const float* pred, const float* gt, int channels, int height, int width, int window, float* scratch,
                    float* ssim_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Ray cache (csrc/ncw_cache.hip): the training rows of ONE image as the reference's dataset builds them for
+ * tools/prepare_data/prepare_data_cache.py (datasets/phototourism.py:150-209, 557-657), without its host round trips.
+ *   ncw_sfm_depth_splat : get_colmap_depth (:150-209) without the dir_norm factor (ncw_cache_rows applies it): the n SfM
+ *                         key-points of the image -- xyz [n,3] f32 world positions, err [n] f32 reprojection errors, px [n,2]
+ *                         int32 (col, row), already rounded -- as planes depth_z [h*w] (camera-space z = row 2 of the HOST
+ *                         world -> camera matrix w2c_host[12] applied to the point; K's last row is (0, 0, 1), so the
+ *                         reference's `intrinsic @ extrinsic` leaves that row as it is; negative z is written as it is) and
+ *                         weight [h*w] = 2 exp(-(err / err_mean)^2); zero where no key-point lands.  Key-points outside
+ *                         [0,w) x [0,h) are ignored.  Where several land on one pixel THE LARGEST INDEX WINS (file order, what
+ *                         numpy / torch-CPU assignment does; the reference's CUDA assignment is unordered): pass 1 is an int32
+ *                         atomicMax into `winner` [h*w] (scratch), pass 2 lets the winner write.  No float atomics: bitwise
+ *                         reproducible.  The three planes are filled by the entry point; n == 0 launches no kernel.
+ *   ncw_cache_rows      : :557-657 for the pixels [p0, p0 + n) of the view (row-major), one thread per pixel:
+ *                         rows [n][ncols] = o(3) d(3) near far ts [label] depth weight 0 (ncols 13 with a label map, 12 with
+ *                         label == NULL: the layout ncw_batch_assemble reads; the reference's code concatenates these columns
+ *                         WITHOUT the last one although its comment and its reader's [10:13] say 13), rgbs [n][3] = float(u8) / 255.f of image [h,w,3] uint8, keep [n] uint8.
+ *                         o, d: ncw_view_rays' arithmetic.  depth = depth_z[p] |((col - cx) / fx, (row - cy) / fy, 1)|.
+ *                         label: nearest sample of the uint8 map [label_h, label_w] at (floor(row label_h / h), floor(col
+ *                         label_w / w)), clamped (stands in for cv2.resize INTER_NEAREST; unpinned against cv2).
+ *                         hit / range: the SfM octrees of gen_octree_from_sfm(expand=1, radius=1) / (expand=2, radius=1.5)
+ *                         (HOST structs; either NULL = use_voxel False: keep = 1 and near / far are the camera's).  keep = 1
+ *                         iff ncw_ray_voxel_near_far's near of the hit octree is > 0; where keep, near / far become the range
+ *                         octree's near and far + voxel_size, or 0 / 0 where it misses.  Rows of dropped pixels are written
+ *                         too (camera near / far).  rows and rgbs must be 16-byte aligned (workgroups write 16-byte stores).
+ * Both return NCW_E_BADARG for NULL / misaligned pointers or a range outside the view, 0 without a launch for n == 0.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct NcwCacheOctree {
+    float origin[3];
+    float scale;
+    int32_t level;
+    int32_t _pad;
+    const uint32_t* occ;
+    const uint32_t* brick;
+} NcwCacheOctree;
+
+int ncw_sfm_depth_splat(const float* xyz, const float* err, const int32_t* px, int64_t n, double err_mean, const float* w2c_host,
+                        int width, int height, int32_t* winner, float* depth_z, float* weight, void* stream);
+int ncw_cache_rows(const NcwViewCamera* cam, const uint8_t* image, const uint8_t* label, int label_h, int label_w,
+                   const float* depth_z, const float* weight, int image_id, float voxel_size, const NcwCacheOctree* hit,
+                   const NcwCacheOctree* range, int64_t p0, int64_t n, int ncols, float* rows, float* rgbs, uint8_t* keep,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,7 @@
 // no float atomics, bitwise reproducible run to run.
 #include "../../include/neuconw_hip.h"
 #include "ncw_common.h"
+#include "ncw_raymath.h"
 
 #include <float.h>
 #include <math.h>
@@ -65,15 +66,8 @@ __global__ __launch_bounds__(VB) void view_rays_kernel(NcwViewCamera cam, int64_
     if (i >= n) return;
     const int64_t p = p0 + i;
     const int row = (int)(p / cam.width), col = (int)(p - (int64_t)row * cam.width);
-    // get_ray_directions: integer pixel coordinates, no +0.5 (ray_utils.py:18-24)
-    const float dx = ((float)col - cam.cx) / cam.fx;
-    const float dy = -((float)row - cam.cy) / cam.fy;
-    const float dz = -1.f;
-    // get_rays: directions @ c2w[:, :3]^T, normalised (ray_utils.py:44-45)
     float d[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) d[k] = dx * cam.c2w[4 * k] + dy * cam.c2w[4 * k + 1] + dz * cam.c2w[4 * k + 2];
-    const float nrm = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    const float nrm = view_ray_dir(cam, row, col, d);
     f32x4 a = {cam.c2w[3], cam.c2w[7], cam.c2w[11], d[0] / nrm};
     f32x4 b = {d[1] / nrm, d[2] / nrm, cam.near, cam.far};
     f32x4* o = reinterpret_cast<f32x4*>(rays + 8 * i);  // rays is 16-byte aligned (checked by the entry point); rows are 32 bytes

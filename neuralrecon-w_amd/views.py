@@ -230,7 +230,8 @@ def render_view(rdr, camera, ts, chunk=DEFAULT_CHUNK, gt=None, label=None, backg
 # ---------------------------------------------------------------------------------------------------
 # the dataset's view (datasets/phototourism.py `val` / `test_train` item)
 # ---------------------------------------------------------------------------------------------------
-def _load_image(path, downscale):
+def _decode_image(path, downscale):
+    """The decoded pixels [h, w, 3] uint8 (RGB, LANCZOS when downscaled: phototourism.py:542-551, 761-764)."""
     try:
         from PIL import Image
     except ImportError as e:  # pragma: no cover
@@ -241,8 +242,13 @@ def _load_image(path, downscale):
     if downscale > 1:  # phototourism.py:761-764
         w, h = w // downscale, h // downscale
         img = img.resize((w, h), Image.LANCZOS)
-    arr = np.asarray(img, dtype=np.uint8)
-    return torch.from_numpy(arr.copy()).permute(2, 0, 1).float().div(255.0), w, h  # ToTensor: [3, h, w] in [0, 1]
+    return np.asarray(img, dtype=np.uint8).copy()
+
+
+def _load_image(path, downscale):
+    arr = _decode_image(path, downscale)
+    h, w = arr.shape[:2]
+    return torch.from_numpy(arr).permute(2, 0, 1).float().div(255.0), w, h  # ToTensor: [3, h, w] in [0, 1]
 
 
 def reference_sfm_path(root_dir):
@@ -254,25 +260,13 @@ def reference_sfm_path(root_dir):
     return "../neuralsfm" if name in ("brandenburg_gate", "palacio_de_bellas_artes") else "sparse"
 
 
-def scene_view(root_dir, image_id=None, img_downscale=1, sfm_path=None, split="val", image_name=None, scene_origin=None,
-               scene_radius=None, load_image=True):
-    """The `val` / `test_train` item of the reference's dataset (datasets/phototourism.py:316-449, 749-802) for one image:
-    returns (Camera, gt [3,h,w] f32 in [0,1] or None, image_id).
-      * sfm_path: the COLMAP model under <root_dir>/dense/; None = the reference's per-scene choice (`reference_sfm_path`);
-      * the images of <root_dir>/*.tsv that are registered in dense/<sfm_path>/images.bin, in file order; the default id is
-        the first training image (`val_id = img_ids_train[0]`); image_name selects by file name;
-      * K rescaled by (size // downscale) / size with the reference's size int(2 cx) x int(2 cy) (:367-375);
-      * c2w = inv(w2c)[:3] with columns 1, 2 negated ("right down front" -> "right up back", :406-408);
-      * near / far: the 0.1 / 99.9 percentiles of the depths of the SfM points in front of the camera, or
-        origin_z -+ 1.5 radius when scene_origin (SfM frame) and scene_radius are given (:426-444);
-      * split 'val' clamps the downscale to >= 8 (:70-71);
-      * the image is decoded with PIL (RGB, LANCZOS when downscaled); the view takes the decoded image's size (:760-769).
-    With load_image=False nothing is decoded: gt is None and the size is the K rescale's."""
-    from . import reproj, voxel
+def read_scene(root_dir, sfm_path=None):
+    """What the reference's dataset reads ONCE per scene (datasets/phototourism.py:316-350, 360, 453-462): the COLMAP model under
+    <root_dir>/dense/<sfm_path> (None = `reference_sfm_path`) and the first *.tsv.  Returns a dict: `sp` (the model directory),
+    `images` / `cams` (reproj.read_images_binary / read_cameras_binary), `tsv`, `by_name` {file name: image id}, `ids` (the tsv's
+    images that are registered in images.bin, file order) and `ids_train` (those whose split is not 'test')."""
+    from . import reproj
 
-    downscale = int(img_downscale)
-    if split == "val":
-        downscale = max(8, downscale)
     if sfm_path is None:
         sfm_path = reference_sfm_path(root_dir)
     sp = os.path.normpath(os.path.join(root_dir, "dense", sfm_path))
@@ -295,19 +289,17 @@ def scene_view(root_dir, image_id=None, img_downscale=1, sfm_path=None, split="v
             ids.append(by_name[row["filename"]])
             if row.get("split") != "test":
                 ids_train.append(ids[-1])
-    if image_name is not None:
-        if image_name not in by_name:
-            raise KeyError("image %r is not in %s" % (image_name, os.path.join(sp, "images.bin")))
-        image_id = by_name[image_name]
-    if image_id is None:
-        if not ids_train:
-            raise ValueError("%s lists no training image registered in images.bin" % sorted(tsvs)[0])
-        image_id = ids_train[0]
-    image_id = int(image_id)
-    if image_id not in images:
-        raise KeyError("image id %d is not in %s" % (image_id, os.path.join(sp, "images.bin")))
-    im = images[image_id]
-    p = cams[im["camera_id"]]["params"]
+    return {"sp": sp, "sfm_path": sfm_path, "images": images, "cams": cams, "tsv": sorted(tsvs)[0], "by_name": by_name, "ids": ids,
+            "ids_train": ids_train}
+
+
+def image_pose(scene, image_id, downscale):
+    """K [3,3] f32 rescaled by (size // downscale) / size with the reference's size int(2 cx) x int(2 cy) (phototourism.py:367-375),
+    w2c [4,4] f64, c2w [3,4] f64 = inv(w2c)[:3] with columns 1, 2 negated (:406-408), and the rescaled size (w, h)."""
+    from . import reproj
+
+    im = scene["images"][image_id]
+    p = scene["cams"][im["camera_id"]]["params"]
     img_w, img_h = int(p[2] * 2), int(p[3] * 2)
     w_, h_ = img_w // downscale, img_h // downscale
     K = np.zeros((3, 3), dtype=np.float32)
@@ -318,19 +310,63 @@ def scene_view(root_dir, image_id=None, img_downscale=1, sfm_path=None, split="v
     w2c[:3, :3], w2c[:3, 3] = reproj.qvec2rotmat(im["qvec"]), im["tvec"]
     c2w = np.linalg.inv(w2c)[:3].copy()
     c2w[:, 1:3] *= -1
+    return K, w2c, c2w, w_, h_
+
+
+def image_near_far(scene, w2c, scene_origin=None, scene_radius=None):
+    """phototourism.py:426-444: the 0.1 / 99.9 percentiles of the depths of the SfM points in front of the camera, or
+    origin_z -+ 1.5 radius when scene_origin (SfM frame) and scene_radius are given.  points3D.bin is read once per scene."""
+    from . import voxel
+
     if scene_origin is not None:
         if scene_radius is None:
             raise ValueError("scene_view: scene_origin needs scene_radius")
         oz = (np.concatenate([np.asarray(scene_origin, dtype=np.float64), np.ones(1)])[None] @ w2c.T)[0, 2]
-        near, far = oz - float(scene_radius) * 1.5, oz + float(scene_radius) * 1.5
-    else:
-        xyz, _, _ = voxel.read_points3d(os.path.join(sp, "points3D.bin"))
-        z = (np.concatenate([xyz, np.ones((len(xyz), 1))], -1) @ w2c.T)[:, 2]
-        z = z[z > 0]
-        near, far = np.percentile(z, 0.1), np.percentile(z, 99.9)
+        return oz - float(scene_radius) * 1.5, oz + float(scene_radius) * 1.5
+    if "xyz_h" not in scene:
+        xyz, _, _ = voxel.read_points3d(os.path.join(scene["sp"], "points3D.bin"))
+        scene["xyz_h"] = np.concatenate([xyz, np.ones((len(xyz), 1))], -1)
+    z = (scene["xyz_h"] @ w2c.T)[:, 2]
+    z = z[z > 0]
+    return np.percentile(z, 0.1), np.percentile(z, 99.9)
+
+
+def scene_view(root_dir, image_id=None, img_downscale=1, sfm_path=None, split="val", image_name=None, scene_origin=None,
+               scene_radius=None, load_image=True):
+    """The `val` / `test_train` item of the reference's dataset (datasets/phototourism.py:316-449, 749-802) for one image:
+    returns (Camera, gt [3,h,w] f32 in [0,1] or None, image_id).
+      * sfm_path: the COLMAP model under <root_dir>/dense/; None = the reference's per-scene choice (`reference_sfm_path`);
+      * the images of <root_dir>/*.tsv that are registered in dense/<sfm_path>/images.bin, in file order; the default id is
+        the first training image (`val_id = img_ids_train[0]`); image_name selects by file name;
+      * K rescaled by (size // downscale) / size with the reference's size int(2 cx) x int(2 cy) (:367-375);
+      * c2w = inv(w2c)[:3] with columns 1, 2 negated ("right down front" -> "right up back", :406-408);
+      * near / far: the 0.1 / 99.9 percentiles of the depths of the SfM points in front of the camera, or
+        origin_z -+ 1.5 radius when scene_origin (SfM frame) and scene_radius are given (:426-444);
+      * split 'val' clamps the downscale to >= 8 (:70-71);
+      * the image is decoded with PIL (RGB, LANCZOS when downscaled); the view takes the decoded image's size (:760-769).
+    With load_image=False nothing is decoded: gt is None and the size is the K rescale's.  The scene files are read by
+    `read_scene` / `image_pose` / `image_near_far`, which cachebuild shares."""
+    downscale = int(img_downscale)
+    if split == "val":
+        downscale = max(8, downscale)
+    scene = read_scene(root_dir, sfm_path)
+    images, by_name, ids_train, sp = scene["images"], scene["by_name"], scene["ids_train"], scene["sp"]
+    if image_name is not None:
+        if image_name not in by_name:
+            raise KeyError("image %r is not in %s" % (image_name, os.path.join(sp, "images.bin")))
+        image_id = by_name[image_name]
+    if image_id is None:
+        if not ids_train:
+            raise ValueError("%s lists no training image registered in images.bin" % scene["tsv"])
+        image_id = ids_train[0]
+    image_id = int(image_id)
+    if image_id not in images:
+        raise KeyError("image id %d is not in %s" % (image_id, os.path.join(sp, "images.bin")))
+    K, w2c, c2w, w_, h_ = image_pose(scene, image_id, downscale)
+    near, far = image_near_far(scene, w2c, scene_origin, scene_radius)
     gt = None
     if load_image:
-        gt, w_, h_ = _load_image(os.path.join(root_dir, "dense", "images", im["name"]), downscale)
+        gt, w_, h_ = _load_image(os.path.join(root_dir, "dense", "images", images[image_id]["name"]), downscale)
     return Camera(K, c2w, w_, h_, near, far), gt, image_id
 
 
