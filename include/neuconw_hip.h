@@ -779,6 +779,42 @@ int ncw_cache_rows(const NcwViewCamera* cam, const uint8_t* image, const uint8_t
                    const NcwCacheOctree* range, int64_t p0, int64_t n, int ncols, float* rows, float* rgbs, uint8_t* keep,
                    void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Area-weighted surface sampling of a triangle mesh (csrc/ncw_surf.hip) for the mesh evaluation: the open3d branch of the
+ * reference scores a predicted MESH by 10 |GT| points drawn uniformly by area from the triangles inside the evaluation box
+ * (utils/eval_utils.py:20-61: `mesh_pred.crop(bbox_gt)` :39, `sample_points_uniformly` :42) and colours the two clouds by
+ * their errors (:116-123, host side: evalmesh.error_colours).  All arithmetic is float64 (GT coordinates are metres far from
+ * the origin, triangles are millimetres); no atomics; every output depends on its own index only, so results are bitwise
+ * reproducible and a range of samples may be split over any number of launches.
+ * UNPINNED against open3d (its source is not at hand): the crop rule -- taken from its documentation: a triangle survives
+ * when all three vertices are inside the box, bounds inclusive --, and the random stream (open3d draws from an unseeded
+ * Mersenne twister: its samples are not reproducible even in the reference).
+ *   ncw_surf_weights : weight[f] = 0.5 |(B - A) x (C - A)| of faces [F,3] int32 over verts [V,3] f64; EXACTLY 0 when a corner
+ *                      index is outside [0, n_verts) (such a corner is never read), when the area is not finite, or when
+ *                      `box` (HOST double[6]: lo xyz, hi xyz; NULL = no crop) is given and any corner lies outside the
+ *                      closed box.
+ *   (caller)         : cdf[f] = inclusive prefix sum of weight in f64, non-decreasing (evalmesh.surface_cdf: torch.cumsum).
+ *   ncw_surf_pick    : tri[i] = the smallest k with cdf[k] > x[i]; when there is none (x >= cdf[F-1]) the smallest k with
+ *                      cdf[k] == cdf[F-1] (the last triangle of positive weight).  NaN or negative x counts as 0.  A triangle
+ *                      of weight 0 (cdf[k] == cdf[k-1], or cdf[0] == 0) is therefore never returned.  n_faces >= 1.
+ *   ncw_surf_sample  : samples i = i0 .. i0 + n - 1 of n_total, one lane each.  (w0, w1, w2, w3) = Philox4x32-10 of counter
+ *                      (lo32(i), hi32(i), 0, 0) under key (lo32(seed), hi32(seed));  xi = (((u64)w0 << 32 | w1) >> 11) 2^-53,
+ *                      r1 = (w2 + 0.5) 2^-32, r2 = (w3 + 0.5) 2^-32;  mode 0 (independent draws, the reference's
+ *                      distribution): u = xi;  mode 1 (stratified): u = (i + xi) / n_total;  k = pick(u cdf[F-1]) with
+ *                      ncw_surf_pick's search;  s = sqrt(r1), pts[i - i0] = (1 - s) A + s (1 - r2) B + s r2 C (open3d's
+ *                      formula; products and sums rounded one by one, no FMA).  tri [n] int32 (k) and urr [n,3] f64
+ *                      (u, r1, r2) are optional (NULL = not written).  The caller guarantees that every face of positive
+ *                      weight has its corners inside verts (ncw_surf_weights' zeros do).  When cdf[F-1] is not > 0 there is
+ *                      nothing to draw from: no face is read, pts are NaN and tri is -1.
+ * All return NCW_E_BADARG for NULL pointers, n_faces outside [1, 2^31) (pick / sample), a bad mode, or (mode 1) a range
+ * outside [0, n_total); 0 without a launch for an empty range.
+ * ---------------------------------------------------------------------------------------- */
+int ncw_surf_weights(const double* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const double* box,
+                     double* weight, void* stream);
+int ncw_surf_pick(const double* cdf, int64_t n_faces, const double* x, int64_t n, int32_t* tri, void* stream);
+int ncw_surf_sample(const double* verts, const int32_t* faces, const double* cdf, int64_t n_faces, uint64_t seed, int64_t i0,
+                    int64_t n, int64_t n_total, int mode, double* pts, int32_t* tri, double* urr, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

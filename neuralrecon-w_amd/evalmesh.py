@@ -13,6 +13,13 @@ the nearest-neighbour queries with one scipy KDTree query per point; here:
   * the SfM crop with sorted unique cell keys + searchsorted instead of the O(N M) Morton-code compare (`sfm_crop`);
   * all thresholds from one sort per distance vector (`metrics`).
 File layout and JSON keys are the reference's.
+
+`eval_mesh(surface=k)` is the reference's OTHER branch (`o3d_load` with is_mesh, utils/eval_utils.py:20-61): the predicted
+mesh is scored by k |GT| points drawn uniformly by area from its triangles inside the evaluation box (csrc/ncw_surf.hip,
+`sample_surface`), not by its vertices; `error_clouds` writes the error-coloured clouds of utils/eval_mesh.py:96-98
+(`visualize_error`, eval_utils.py:116-123).  Unpinned against open3d, whose source is not at hand: its crop rule (taken from
+its documentation), its Mersenne-twister stream (unseeded in the reference: not reproducible there either; ours is
+Philox4x32-10 of (sample index, seed)) and its double -> uchar colour rounding.
 """
 import ctypes as C
 import json
@@ -286,7 +293,17 @@ def read_points3d_filtered(path, track_length, reproj_error, sfm_to_gt=None):
 # crops and metrics
 # ---------------------------------------------------------------------------------------------------
 def bbx_crop(points, bbx):
-    """utils/eval_utils.py:103-113: the points strictly inside the box (normalised coordinates in the open (-1, 1)^3)."""
+    """utils/eval_utils.py:103-113: the points strictly inside the box (normalised coordinates in the open (-1, 1)^3).
+    A torch tensor (any device) is cropped on its device with the same float64 arithmetic and returned as a float64 tensor
+    there; anything else goes through numpy."""
+    if torch.is_tensor(points):
+        p = points.reshape(-1, 3).double()
+        bmin = torch.tensor([float(v) for v in bbx[0]], dtype=torch.float64, device=p.device)
+        bmax = torch.tensor([float(v) for v in bbx[1]], dtype=torch.float64, device=p.device)
+        origin = bmin + (bmax - bmin) / 2
+        scale = (bmax - bmin) / 2
+        pn = (p - origin) / scale
+        return p[(pn > -1).all(-1) & (pn < 1).all(-1)]
     points = np.asarray(points, dtype=np.float64).reshape(-1, 3)
     bmin, bmax = np.array(bbx[0], dtype=np.float64), np.array(bbx[1], dtype=np.float64)
     origin = bmin + (bmax - bmin) / 2
@@ -295,13 +312,48 @@ def bbx_crop(points, bbx):
     return points[(pn > -1).all(-1) & (pn < 1).all(-1)]
 
 
+def _sfm_crop_torch(points, sfm_points, voxel_size, bbx):
+    """`sfm_crop` for a tensor: the same float64 operations in the same order, on the tensor's device."""
+    p = points.reshape(-1, 3).double()
+    dev = p.device
+    if torch.is_tensor(sfm_points):
+        sp = sfm_points.reshape(-1, 3).double().to(dev)
+    else:
+        sp = torch.from_numpy(np.ascontiguousarray(sfm_points, dtype=np.float64).reshape(-1, 3)).to(dev)
+    bmin, bmax = np.array(bbx[0], dtype=np.float64), np.array(bbx[1], dtype=np.float64)
+    dim = np.max(bmax - bmin)
+    origin = torch.from_numpy(bmin + (bmax - bmin) / 2).to(dev)
+    scale = float(dim / 2)
+    res = int(np.floor(2 * scale / voxel_size))
+
+    def cells(x):
+        q = torch.floor(res * ((x - origin) / scale + 1.0) / 2.0)
+        ok = ((q >= 0) & (q < res)).all(-1)
+        qi = torch.where(ok[:, None], q, torch.zeros_like(q)).long()
+        return (qi[:, 0] * res + qi[:, 1]) * res + qi[:, 2], ok
+
+    if p.shape[0] == 0 or sp.shape[0] == 0:
+        return p[:0]
+    sk, sok = cells(sp)
+    sk = torch.unique(sk[sok])
+    pk, pok = cells(p)
+    if sk.shape[0] == 0:
+        return p[:0]
+    pos = torch.clamp(torch.searchsorted(sk, pk), 0, sk.shape[0] - 1)
+    return p[pok & (sk[pos] == pk)]
+
+
 def sfm_crop(points, sfm_points, voxel_size, bbx):
     """utils/eval_utils.py:176-216 `point_crop`: keep the points whose voxel holds an SfM point.  Cube of half-size
     (longest box edge) / 2 around the box centre, res = floor(2 scale / voxel_size), cell = floor(res (x + 1) / 2) per axis
     with NO clamp.  The reference compares every point's kaolin Morton code against every SfM code (O(N M)); here sorted
     unique cell keys + searchsorted.  One difference: SfM cells outside [0, res)^3 are dropped.  In the reference such a cell
     could only match through kaolin's Morton code of negative / overflowing int16 coordinates, which cannot be pinned
-    without kaolin; points outside the cube therefore never survive the crop here."""
+    without kaolin; points outside the cube therefore never survive the crop here.
+    `points` as a torch tensor (any device) is cropped on its device -- same float64 arithmetic, same comparisons -- and
+    returned as a float64 tensor there (`sfm_points` may be numpy or a tensor)."""
+    if torch.is_tensor(points):
+        return _sfm_crop_torch(points, sfm_points, voxel_size, bbx)
     points = np.asarray(points, dtype=np.float64).reshape(-1, 3)
     sfm_points = np.asarray(sfm_points, dtype=np.float64).reshape(-1, 3)
     bmin, bmax = np.array(bbx[0], dtype=np.float64), np.array(bbx[1], dtype=np.float64)
@@ -368,7 +420,159 @@ def metrics(d_gt_to_pred, d_pred_to_gt, thresholds):
 
 
 # ---------------------------------------------------------------------------------------------------
-# the evaluation (utils/eval_mesh.py:48-123, use_o3d=False)
+# area-weighted surface samples (csrc/ncw_surf.hip; utils/eval_utils.py:39-43)
+# ---------------------------------------------------------------------------------------------------
+SURFACE_MODES = {"iid": 0, "stratified": 1}
+
+
+def _cuda_device(device, what):
+    if device is None:
+        if not torch.cuda.is_available():
+            raise L.NeuconwHipError("evalmesh.%s: no GPU; there is no CPU fallback" % what)
+        return torch.device("cuda", torch.cuda.current_device())
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise L.NeuconwHipError("evalmesh.%s runs on a GPU only; there is no CPU fallback" % what)
+    return dev
+
+
+def _box6(box):
+    if box is None:
+        return None
+    lo, hi = [float(v) for v in box[0]][:3], [float(v) for v in box[1]][:3]
+    if len(lo) != 3 or len(hi) != 3:
+        raise ValueError("box: [[x0, y0, z0], [x1, y1, z1]]")
+    return (C.c_double * 6)(*(lo + hi))
+
+
+@torch.no_grad()
+def surface_weights(verts, faces, box=None):
+    """ncw_surf_weights: float64 [F] triangle areas of faces (int32 [F,3], device) over verts (float64 [V,3], device);
+    exactly 0 for a corner index outside [0, V), a non-finite area, or -- with `box` = [lo, hi] -- a corner outside the
+    closed box (open3d's documented `TriangleMesh.crop` rule; unpinned)."""
+    if not (verts.is_cuda and faces.is_cuda):
+        raise L.NeuconwHipError("evalmesh.surface_weights: the mesh is not on a GPU; there is no CPU fallback")
+    assert verts.dtype == torch.float64 and faces.dtype == torch.int32
+    verts, faces = verts.reshape(-1, 3).contiguous(), faces.reshape(-1, 3).contiguous()
+    w = torch.empty(faces.shape[0], dtype=torch.float64, device=verts.device)
+    L.check(L.get_lib().ncw_surf_weights(L.ptr(verts), verts.shape[0], L.ptr(faces), faces.shape[0], _box6(box), L.ptr(w),
+                                         L.stream_ptr(verts.device)), "ncw_surf_weights")
+    return w
+
+
+@torch.no_grad()
+def surface_cdf(weight):
+    """The table ncw_surf_pick / ncw_surf_sample search: the inclusive prefix sum of the weights in float64
+    (torch.cumsum), made safe against the scan's rounding.  A parallel prefix sum adds in a different order at every
+    position, so next to a triangle of weight 0 it may differ from its neighbour in the last bit, and such a triangle could
+    then be drawn (its corners may be out of range).  Here an entry of weight 0 is replaced by the running maximum of the
+    entries before it, and the whole table is made non-decreasing by that running maximum: a zero-weight triangle repeats
+    its predecessor exactly and can never be returned."""
+    cdf = torch.cumsum(weight.double(), 0)
+    if cdf.numel() == 0:
+        return cdf
+    return torch.cummax(torch.where(weight > 0, cdf, torch.zeros_like(cdf)), 0).values.contiguous()
+
+
+@torch.no_grad()
+def sample_surface(verts, faces, n, seed=0, mode="stratified", box=None, return_index=False, chunk=None, device=None):
+    """`n` points drawn uniformly by area from the triangles of a mesh (open3d's `sample_points_uniformly`,
+    utils/eval_utils.py:42, after `crop(box)`, :39) on the GPU: float64 [n,3] on the device, and with `return_index` the
+    int32 [n] triangle of every point.  verts [V,3] (numpy or tensor; used as float64), faces [F,3] (numpy or tensor of an
+    INTEGER dtype, checked here; corner indices outside [0, V) give the triangle weight 0).  `box` = [lo, hi] keeps the
+    triangles with all three corners inside the closed box.  mode "stratified" (default): sample i searches
+    u = (i + xi_i) / n of the area table, so every triangle gets floor or ceil of its share and a wavefront's searches stay
+    together; "iid": u = xi_i, independent draws (the reference's distribution).  Either way each point is uniform over
+    the surface.  The stream is Philox4x32-10 of (i, seed): the same (seed, n, mode) gives the same points bit for bit, for
+    any `chunk` (samples per launch; None = one launch).  An empty mesh or a total weight of 0 returns [0,3].  No CPU
+    fallback: NeuconwHipError without a GPU."""
+    if mode not in SURFACE_MODES:
+        raise ValueError("mode: one of %s (got %r)" % (", ".join(sorted(SURFACE_MODES)), mode))
+    f = faces if torch.is_tensor(faces) else torch.as_tensor(np.asarray(faces))
+    if f.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8) or f.dim() != 2 or f.shape[1] != 3:
+        raise ValueError("faces: an integer array of shape [F,3] (got %s %s)" % (f.dtype, tuple(f.shape)))
+    n = int(n)
+    if n < 0:
+        raise ValueError("n must not be negative")
+    if device is None and torch.is_tensor(verts) and verts.is_cuda:
+        device = verts.device
+    dev = _cuda_device(device, "sample_surface")
+    v = verts if torch.is_tensor(verts) else torch.from_numpy(np.ascontiguousarray(verts, dtype=np.float64))
+    v = v.detach().reshape(-1, 3).to(dev).double().contiguous()
+    f = f.detach().to(dev).long()
+    if f.shape[0] >= (1 << 31):
+        raise ValueError("at most 2^31 - 1 faces")
+    # an index that does not fit int32 must stay out of range after the cast
+    f = torch.where((f < 0) | (f >= v.shape[0]), torch.full_like(f, -1), f).int().contiguous()
+    pts = torch.empty(n, 3, dtype=torch.float64, device=dev)
+    tri = torch.empty(n, dtype=torch.int32, device=dev) if return_index else None
+    total = 0.0
+    if f.shape[0] and v.shape[0] and n:
+        cdf = surface_cdf(surface_weights(v, f, box))
+        total = float(cdf[-1])  # one device -> host read
+    if not (total > 0.0):
+        return (pts[:0], tri[:0]) if return_index else pts[:0]
+    lib, s = L.get_lib(), L.stream_ptr(dev)
+    step = n if chunk is None else max(1, int(chunk))
+    for i0 in range(0, n, step):
+        c = min(step, n - i0)
+        L.check(lib.ncw_surf_sample(L.ptr(v), L.ptr(f), L.ptr(cdf), f.shape[0], int(seed) & 0xFFFFFFFFFFFFFFFF, i0, c, n,
+                                    SURFACE_MODES[mode], L.ptr(pts[i0:i0 + c]), L.ptr(tri[i0:i0 + c]) if return_index else None,
+                                    None, s), "ncw_surf_sample")
+    return (pts, tri) if return_index else pts
+
+
+# ---------------------------------------------------------------------------------------------------
+# error-coloured clouds (utils/eval_utils.py:116-123 `visualize_error`)
+# ---------------------------------------------------------------------------------------------------
+# matplotlib's "jet": piecewise-linear (x, y) nodes per channel
+_JET_NODES = {
+    0: ((0.00, 0.0), (0.35, 0.0), (0.66, 1.0), (0.89, 1.0), (1.00, 0.5)),
+    1: ((0.000, 0.0), (0.125, 0.0), (0.375, 1.0), (0.640, 1.0), (0.910, 0.0), (1.000, 0.0)),
+    2: ((0.00, 0.5), (0.11, 1.0), (0.34, 1.0), (0.65, 0.0), (1.00, 0.0)),
+}
+
+
+def _jet_table(n=256):
+    """The n-entry table matplotlib samples from jet's piecewise-linear definition: entry j is the interpolant at j of the
+    nodes stretched to [0, n - 1] (first and last entries are the end nodes), clipped to [0, 1].  float64 [n,3]."""
+    out = np.empty((n, 3), dtype=np.float64)
+    xi = (n - 1) * np.linspace(0, 1, n)
+    for ch, nodes in _JET_NODES.items():
+        a = np.array(nodes, dtype=np.float64)
+        x, y = a[:, 0] * (n - 1), a[:, 1]
+        ind = np.searchsorted(x, xi)[1:-1]
+        t = (xi[1:-1] - x[ind - 1]) / (x[ind] - x[ind - 1])
+        out[:, ch] = np.clip(np.concatenate([[y[0]], t * (y[ind] - y[ind - 1]) + y[ind - 1], [y[-1]]]), 0.0, 1.0)
+    return out
+
+
+JET = _jet_table()
+JET_U8 = np.round(255.0 * JET).astype(np.uint8)
+
+
+@torch.no_grad()
+def error_colours(dists, threshold):
+    """uint8 [n,3] colours of `visualize_error`: v = min(d, 3 t) / (3 t) in float64, looked up in the 256-entry jet table
+    at min(int(256 v), 255) (what matplotlib's colormap call does with a float), channel = round(255 c).  open3d's own
+    double -> uchar conversion when it writes the cloud is unpinned; round-to-nearest is our choice.  Runs on the device
+    of `dists` (tensor) or on the host (numpy)."""
+    d = _as_f64(dists)
+    max_dist = float(threshold) * 3
+    v = torch.clamp(d, max=max_dist) / max_dist
+    idx = torch.clamp((v * 256).long(), 0, 255)
+    return torch.from_numpy(JET_U8).to(d.device)[idx]
+
+
+def _write_error_cloud(path, pts, dists, threshold):
+    from . import reproj
+
+    xyz = pts.detach().cpu().numpy() if torch.is_tensor(pts) else pts
+    reproj.write_ply_points(path, xyz, error_colours(dists, threshold).cpu().numpy())
+
+
+# ---------------------------------------------------------------------------------------------------
+# the evaluation (utils/eval_mesh.py:48-123, both branches)
 # ---------------------------------------------------------------------------------------------------
 def _write_points(path, pts):
     from . import mesh
@@ -378,7 +582,7 @@ def _write_points(path, pts):
 
 
 def eval_mesh(file_pred, file_trgt, scene_config, is_mesh, threshold=.1, bbx_name="eval_bbx", save_name="eval", sfm=None,
-              device=None, verbose=True):
+              device=None, verbose=True, surface=None, surface_seed=0, surface_mode="stratified", error_clouds=None):
     """utils/eval_mesh.py:48-123 with use_o3d=False: load both PLYs (read_ply_points; `is_mesh` is accepted and, as in the
     reference's trimesh branch, not used), carry the prediction to GT coordinates by scene_config['sfm2gt'], crop both to
     scene_config[bbx_name], optionally crop both to the voxels of the filtered SfM points, nearest neighbours in both
@@ -386,7 +590,19 @@ def eval_mesh(file_pred, file_trgt, scene_config, is_mesh, threshold=.1, bbx_nam
     reference's scene_config keys sfm_path / eval_tl / eval_error / eval_voxel.  Writes under
     <dir of file_pred>/eval_<save_name>/: down_gt.ply, down_pred_in_gt.ply, [sfm_points.ply, pred_filtered.ply,
     target_filtered.ply], visualize/<t:.2f>/metrics.json and metrics.json (thresholds, fscores, precs, recals).  Returns the
-    last threshold's metrics dict."""
+    last threshold's metrics dict.
+
+    `surface` = k (a number; the reference's value is 10) scores the prediction by its SURFACE, as the reference's open3d
+    branch does with is_mesh (utils/eval_utils.py:30-43): file_pred must have faces (reproj.read_ply_mesh, vertices as
+    stored); its vertices are carried to GT coordinates, the triangles with all three corners inside the closed box are kept
+    (open3d's documented crop rule; unpinned), int(|cropped GT|) * k points are drawn uniformly by area on the GPU
+    (`sample_surface` with surface_seed / surface_mode) and written to down_pred_in_gt.ply as doubles (open3d's
+    write_point_cloud); as in the reference no point-wise box crop follows.  The SfM crop of the samples runs on the device
+    (pred_filtered.ply: doubles too).  surface=None is the vertex scoring described above, whatever `is_mesh` is.
+
+    `error_clouds`: None, True (every threshold) or a list of thresholds: writes visualize/<t:.2f>/error_pred_precision.ply
+    (the predicted points coloured by their distance to GT) and error_gt_recal.ply (the GT points by their distance to the
+    prediction), colours by `error_colours` (utils/eval_mesh.py:96-98)."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     save_dir = os.path.join(os.path.dirname(file_pred), "eval_" + str(save_name))
     os.makedirs(save_dir, exist_ok=True)
@@ -396,8 +612,20 @@ def eval_mesh(file_pred, file_trgt, scene_config, is_mesh, threshold=.1, bbx_nam
 
     verts_trgt = bbx_crop(read_ply_points(file_trgt), scene_config[bbx_name])
     _write_points(os.path.join(save_dir, "down_gt.ply"), verts_trgt)
-    verts_pred = bbx_crop(apply_transform(read_ply_points(file_pred), sfm_to_gt), scene_config[bbx_name])
-    _write_points(os.path.join(save_dir, "down_pred_in_gt.ply"), verts_pred)
+    if surface is None:
+        verts_pred = bbx_crop(apply_transform(read_ply_points(file_pred), sfm_to_gt), scene_config[bbx_name])
+        _write_points(os.path.join(save_dir, "down_pred_in_gt.ply"), verts_pred)
+    else:
+        from . import reproj  # reproj imports this module: bound here, not at import time
+
+        m_verts, m_faces, _ = reproj.read_ply_mesh(file_pred)
+        if m_faces.shape[0] == 0:
+            raise ValueError("%s has no faces: surface sampling needs a triangle mesh (surface=None scores points)" % file_pred)
+        n_samples = int(int(verts_trgt.shape[0]) * surface)
+        verts_pred = sample_surface(apply_transform(m_verts, sfm_to_gt), m_faces, n_samples, seed=surface_seed,
+                                    mode=surface_mode, box=scene_config[bbx_name], device=dev)
+        log("surface samples: %d" % verts_pred.shape[0])
+        reproj.write_ply_points(os.path.join(save_dir, "down_pred_in_gt.ply"), verts_pred.cpu().numpy())
 
     if sfm is None and "sfm_path" in scene_config:
         sfm = {"path": scene_config["sfm_path"], "track_length": scene_config["eval_tl"],
@@ -407,11 +635,14 @@ def eval_mesh(file_pred, file_trgt, scene_config, is_mesh, threshold=.1, bbx_nam
         _write_points(os.path.join(save_dir, "sfm_points.ply"), sfm_pts)
         log("filtered points: %d" % sfm_pts.shape[0])
         verts_pred = sfm_crop(verts_pred, sfm_pts, sfm["voxel_size"], scene_config[bbx_name])
-        _write_points(os.path.join(save_dir, "pred_filtered.ply"), verts_pred)
+        if torch.is_tensor(verts_pred):
+            reproj.write_ply_points(os.path.join(save_dir, "pred_filtered.ply"), verts_pred.cpu().numpy())
+        else:
+            _write_points(os.path.join(save_dir, "pred_filtered.ply"), verts_pred)
         verts_trgt = sfm_crop(verts_trgt, sfm_pts, sfm["voxel_size"], scene_config[bbx_name])
         _write_points(os.path.join(save_dir, "target_filtered.ply"), verts_trgt)
 
-    p = torch.from_numpy(verts_pred).to(dev)
+    p = verts_pred if torch.is_tensor(verts_pred) else torch.from_numpy(verts_pred).to(dev)
     g = torch.from_numpy(verts_trgt).to(dev)
     dist1, _ = nn_distances(p, g)  # for every GT point its nearest prediction (eval_mesh.py:88)
     dist2, _ = nn_distances(g, p)  # for every predicted point its nearest GT point (:89)
@@ -427,6 +658,12 @@ def eval_mesh(file_pred, file_trgt, scene_config, is_mesh, threshold=.1, bbx_nam
         fscores.append(m["fscore"])
         precs.append(m["prec"])
         recals.append(m["recal"])
+    if error_clouds is not None and error_clouds is not False:
+        for t in (thresholds if error_clouds is True else list(error_clouds)):
+            save_path = os.path.join(save_dir, "visualize", "%.2f" % t)
+            os.makedirs(save_path, exist_ok=True)
+            _write_error_cloud(os.path.join(save_path, "error_pred_precision.ply"), p, dist2, t)
+            _write_error_cloud(os.path.join(save_path, "error_gt_recal.ply"), g, dist1, t)
     with open(os.path.join(save_dir, "metrics.json"), "w") as fh:
         json.dump({"thresholds": [float(t) for t in thresholds], "fscores": fscores, "precs": precs, "recals": recals}, fh)
     log("fscores: %s" % fscores)

@@ -454,11 +454,13 @@ SCENES = {
 }
 
 
-def eval_pipeline(scene_name, pred_dir, data_root="data/heritage-recon", verbose=True):
+def eval_pipeline(scene_name, pred_dir, data_root="data/heritage-recon", verbose=True, surface=None, surface_seed=0,
+                  surface_mode="stratified", error_clouds=None):
     """scripts/eval_pipeline.sh in one process: the reprojection filter of <pred_dir>/mesh/extracted_mesh_level_10_colored.ply
     against itself (written to <pred_dir>/mesh/reprojected.ply), then evalmesh.eval_mesh of that file against
     <data_root>/<scene>/<scene>.ply with the scene's thresholds and the SfM crop of <data_root>/<scene>/neuralsfm, results in
-    <pred_dir>/mesh/eval_<scene>_reprojected.ply/.  Returns the last threshold's metrics."""
+    <pred_dir>/mesh/eval_<scene>_reprojected.ply/.  surface / surface_seed / surface_mode / error_clouds go to eval_mesh as
+    they are (reprojected.ply is a point cloud, so `surface` is refused there).  Returns the last threshold's metrics."""
     if scene_name not in SCENES:
         raise ValueError("Not supported scene: %s (one of %s)" % (scene_name, ", ".join(sorted(SCENES))))
     sc = SCENES[scene_name]
@@ -472,4 +474,5 @@ def eval_pipeline(scene_name, pred_dir, data_root="data/heritage-recon", verbose
            "reproj_error": sc["reproj_error"], "voxel_size": sc["voxel_size"]}
     return evalmesh.eval_mesh(os.path.join(pred_path, "reprojected.ply"), os.path.join(scene_dir, scene_name + ".ply"),
                               scene_config, False, threshold=evalmesh.parse_thresholds(sc["thresholds"]), bbx_name="eval_bbx",
-                              save_name=scene_name + "_reprojected.ply", sfm=sfm, verbose=verbose)
+                              save_name=scene_name + "_reprojected.ply", sfm=sfm, verbose=verbose, surface=surface,
+                              surface_seed=surface_seed, surface_mode=surface_mode, error_clouds=error_clouds)

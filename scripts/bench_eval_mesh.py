@@ -9,6 +9,14 @@ plus a few far outliers among the queries (the brute-force escape path).  Times 
 shell search, escape pass), metrics.  When scipy imports, `cKDTree.query(workers=16)` on the same float64 clouds is timed
 beside it as a CPU comparison.  Kernel names for `rocprofv3 --kernel-trace --stats`: nn_cell_keys_kernel,
 nn_cell_ranges_kernel, nn_query_kernel, nn_brute_kernel, nn_brute_finish_kernel.
+
+Surface sampling row (`surface_sampling` in the JSON line; --surf_samples 0 skips it): --surf_samples points (10 M) drawn by
+area from a lat-long mesh of the same wavy sphere with --surf_faces triangles (2 M), float64.  The fused launch
+(ncw_surf_sample, stratified and iid) is timed against the same distribution composed from torch ops on the same area
+table: torch.rand x 3, torch.searchsorted, one gather of the faces, three gathers of the corners, the point formula.  Next
+to each time: the bytes it moves.  For the fused kernel that is what the algorithm needs (area table, faces and vertices
+read once, 24 bytes written per sample); for the composition it is the operand and result sizes of every torch op summed
+(`composed_bytes`).  Kernel names: surf_weights_kernel, surf_sample_kernel.
 """
 import argparse
 import json
@@ -49,6 +57,72 @@ def timed(fn, reps):
     return out, float(np.median(ts))
 
 
+def sphere_mesh(n_faces, dev):
+    """Lat-long mesh of the wavy sphere: (float64 [V,3], int32 [F,3]) on the device, F = 2 q^2 close to n_faces."""
+    q = max(2, int(round((n_faces / 2.0) ** 0.5)))
+    th = torch.linspace(0.05, np.pi - 0.05, q + 1, dtype=torch.float64, device=dev)
+    ph = torch.linspace(0.0, 2 * np.pi, q + 1, dtype=torch.float64, device=dev)
+    T, P = torch.meshgrid(th, ph, indexing="ij")
+    r = 20.0 * (1.0 + 0.1 * torch.sin(5 * T) * torch.cos(4 * P))
+    v = torch.stack([r * torch.sin(T) * torch.cos(P), r * torch.sin(T) * torch.sin(P), r * torch.cos(T)], -1).reshape(-1, 3)
+    v = v + torch.tensor([500.0, -300.0, 40.0], dtype=torch.float64, device=dev)
+    i, j = torch.meshgrid(torch.arange(q, device=dev), torch.arange(q, device=dev), indexing="ij")
+    a = (i * (q + 1) + j).reshape(-1)
+    f = torch.cat([torch.stack([a, a + q + 1, a + 1], -1), torch.stack([a + 1, a + q + 1, a + q + 2], -1)])
+    return v.contiguous(), f.int().contiguous()
+
+
+def composed_sample(verts, faces64, cdf, n):
+    """The fused kernel's distribution (iid) from torch ops; returns (points, bytes moved by the ops)."""
+    dev, b = verts.device, 0
+    u = torch.rand(n, dtype=torch.float64, device=dev)
+    r1 = torch.rand(n, dtype=torch.float64, device=dev)
+    r2 = torch.rand(n, dtype=torch.float64, device=dev)
+    b += 3 * 8 * n
+    x = u * cdf[-1]
+    b += 16 * n
+    k = torch.searchsorted(cdf, x, right=True).clamp_(max=cdf.shape[0] - 1)
+    b += 16 * n + 8 * cdf.shape[0] + 16 * n
+    f = faces64[k]
+    b += 8 * n + 24 * n + 24 * faces64.shape[0]
+    A, B, Cc = verts[f[:, 0]], verts[f[:, 1]], verts[f[:, 2]]
+    b += 3 * (8 * n + 8 * n + 24 * n) + 24 * verts.shape[0]  # column copy, index read, rows written; the table once
+    s = torch.sqrt(r1)
+    wa, wb, wc = 1.0 - s, s * (1.0 - r2), s * r2
+    b += 16 * n + 16 * n + (16 * n + 24 * n) + 24 * n
+    p = wa[:, None] * A + wb[:, None] * B + wc[:, None] * Cc
+    b += 3 * (8 * n + 48 * n) + 2 * 72 * n
+    return p, b
+
+
+def bench_surface(args, dev, res):
+    lib = evalmesh.L.get_lib()
+    v, f = sphere_mesh(args.surf_faces, dev)
+    n, nf = args.surf_samples, int(f.shape[0])
+    out = {"n_samples": n, "n_faces": nf, "n_verts": int(v.shape[0])}
+    cdf, out["weights_and_cdf_ms"] = timed(lambda: evalmesh.surface_cdf(evalmesh.surface_weights(v, f)), args.reps)
+    pts = torch.empty(n, 3, dtype=torch.float64, device=dev)
+
+    def fused(mode):
+        evalmesh.L.check(lib.ncw_surf_sample(evalmesh.L.ptr(v), evalmesh.L.ptr(f), evalmesh.L.ptr(cdf), nf, 1, 0, n, n, mode,
+                                             evalmesh.L.ptr(pts), None, None, evalmesh.L.stream_ptr(dev)), "ncw_surf_sample")
+        return pts
+
+    fused_bytes = 24 * n + 8 * nf + 12 * nf + 24 * int(v.shape[0])
+    for mode, name in ((1, "stratified"), (0, "iid")):
+        _, ms = timed(lambda: fused(mode), args.reps)
+        out["fused_%s_ms" % name] = ms
+        out["fused_%s_GBps" % name] = fused_bytes / ms * 1e-6
+    out["fused_GB_moved"] = fused_bytes * 1e-9
+    f64 = f.long()
+    (p, cb), out["composed_torch_ms"] = timed(lambda: composed_sample(v, f64, cdf, n), args.reps)
+    out["composed_GB_moved"] = cb * 1e-9
+    out["composed_over_fused_iid"] = out["composed_torch_ms"] / out["fused_iid_ms"]
+    # both draw from the same surface: the means agree to sampling noise (radius 20 m, n samples)
+    out["mean_diff_m"] = float((p.mean(0) - fused(0).mean(0)).abs().max())
+    res["surface_sampling"] = out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n_query", type=int, default=1_000_000)
@@ -56,6 +130,8 @@ def main():
     ap.add_argument("--outliers", type=int, default=64)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--no_cpu", action="store_true", help="skip the scipy cKDTree comparison")
+    ap.add_argument("--surf_samples", type=int, default=10_000_000, help="surface sampling row: samples (0 = skip the row)")
+    ap.add_argument("--surf_faces", type=int, default=2_000_000, help="surface sampling row: triangles of the mesh")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     P = surface(args.n_ref, 1)
@@ -90,6 +166,8 @@ def main():
             t2 = time.perf_counter()
             res["cpu_comparison_scipy_ckdtree"] = {"build_ms": 1e3 * (t1 - t0), "query_ms_q_to_p_workers16": 1e3 * (t2 - t1)}
             res["max_abs_diff_vs_ckdtree"] = float(np.max(np.abs(d_qp.double().cpu().numpy() - dk)))
+    if args.surf_samples > 0:
+        bench_surface(args, dev, res)
     print(json.dumps(res))
 
 

@@ -8,7 +8,12 @@ ground-truth cloud, nearest neighbours on the GPU (neuralrecon_w_amd.evalmesh).
 
   * --threshold: "start,end,interval" = np.arange(start, end, interval) like the reference, or one value ("0.1");
   * results under <dir of file_pred>/eval_<save_name>/ (the reference's layout: down_gt.ply, down_pred_in_gt.ply, the SfM
-    crop's sfm_points.ply / pred_filtered.ply / target_filtered.ply, visualize/<t>/metrics.json, metrics.json).
+    crop's sfm_points.ply / pred_filtered.ply / target_filtered.ply, visualize/<t>/metrics.json, metrics.json);
+  * --mesh is accepted and, as in the reference's trimesh branch, changes nothing: the prediction is scored by its vertices;
+  * --sample_surface [K] (K = 10 when omitted, the reference's value) scores a predicted MESH by its surface, as the
+    reference's open3d branch does with --mesh: K |GT| points drawn uniformly by area on the GPU from the triangles inside
+    the box (--surface_seed, --surface_mode iid|stratified);
+  * --error_clouds also writes visualize/<t>/error_pred_precision.ply and error_gt_recal.ply (jet colours of the errors).
 """
 import argparse
 import os
@@ -34,6 +39,12 @@ def get_opts(argv=None):
     ap.add_argument("--reproj_error", type=float, help="mean reprojection error threshold for sfm points")
     ap.add_argument("--voxel_size", type=float, help="voxel size for sfm points to crop point clouds")
     ap.add_argument("--save_name", type=str, default="eval", help="results go to eval_<save_name>")
+    ap.add_argument("--sample_surface", type=float, nargs="?", const=10, default=None, metavar="K",
+                    help="score the predicted mesh by K * |GT| area-weighted surface samples (K = 10 when omitted)")
+    ap.add_argument("--surface_seed", type=int, default=0, help="seed of the surface samples")
+    ap.add_argument("--surface_mode", choices=["iid", "stratified"], default="stratified", help="how the samples are drawn")
+    ap.add_argument("--error_clouds", default=False, action="store_true",
+                    help="write the error-coloured clouds of every threshold")
     return ap.parse_args(argv)
 
 
@@ -51,7 +62,8 @@ def main(argv=None):
         sfm = {"path": args.sfm_path, "track_length": args.track_lenth, "reproj_error": args.reproj_error,
                "voxel_size": args.voxel_size}
     evalmesh.eval_mesh(args.file_pred, args.file_trgt, scene_config, args.mesh, threshold=thresholds, bbx_name=args.bbx_name,
-                       save_name=args.save_name, sfm=sfm)
+                       save_name=args.save_name, sfm=sfm, surface=args.sample_surface, surface_seed=args.surface_seed,
+                       surface_mode=args.surface_mode, error_clouds=True if args.error_clouds else None)
 
 
 if __name__ == "__main__":

@@ -9,6 +9,9 @@ Reads <pred_dir>/mesh/extracted_mesh_level_10_colored.ply, <data_root>/<scene>/{
 <scene>.ply, neuralsfm/points3D.bin}; writes <pred_dir>/mesh/reprojected.ply and
 <pred_dir>/mesh/eval_<scene>_reprojected.ply/.  As in the reference, eval_mesh applies sfm2gt to the filtered cloud that is
 already in GT coordinates: the two steps chain correctly only when sfm2gt is the identity.
+
+--sample_surface / --surface_seed / --surface_mode / --error_clouds are handed to eval_mesh as scripts/eval_mesh.py does.
+The file the pipeline scores, reprojected.ply, is a point cloud: --sample_surface needs faces and is refused on it.
 """
 import argparse
 import os
@@ -23,13 +26,21 @@ def parse_args(argv=None):
     ap.add_argument("--scene_name", required=True, choices=sorted(reproj.SCENES))
     ap.add_argument("--pred_dir", required=True, help="run directory holding mesh/extracted_mesh_level_10_colored.ply")
     ap.add_argument("--data_root", default="data/heritage-recon", help="Heritage-Recon root")
+    ap.add_argument("--sample_surface", type=float, nargs="?", const=10, default=None, metavar="K",
+                    help="score the prediction by K * |GT| area-weighted surface samples (needs a file with faces)")
+    ap.add_argument("--surface_seed", type=int, default=0, help="seed of the surface samples")
+    ap.add_argument("--surface_mode", choices=["iid", "stratified"], default="stratified", help="how the samples are drawn")
+    ap.add_argument("--error_clouds", default=False, action="store_true",
+                    help="write the error-coloured clouds of every threshold")
     return ap.parse_args(argv)
 
 
 def main(argv=None):
     args = parse_args(argv)
     print("Evaluating %s ..." % args.pred_dir)
-    reproj.eval_pipeline(args.scene_name, args.pred_dir, args.data_root)
+    reproj.eval_pipeline(args.scene_name, args.pred_dir, args.data_root, surface=args.sample_surface,
+                         surface_seed=args.surface_seed, surface_mode=args.surface_mode,
+                         error_clouds=True if args.error_clouds else None)
 
 
 if __name__ == "__main__":
