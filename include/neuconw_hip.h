@@ -780,6 +780,48 @@ int ncw_cache_rows(const NcwViewCamera* cam, const uint8_t* image, const uint8_t
                    void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Voxel first-hit views (csrc/ncw_voxview.hip): the point-cloud source of the reprojection filter.  The reference voxelises
+ * the source cloud over the evaluation box (utils/kaolin_renderer.py:16-17: gen_octree(..., expand=0, in_sfm=False)), traces
+ * every pixel of every training view to the first occupied voxel (:110-141) and keeps the target points whose voxel some
+ * view saw (utils/reproj_filter.py:195-196, 224-225, 234-240).  UNPINNED against kaolin (its source is not in the reference
+ * tree): as for ncw_ray_voxel_trace the contract followed is its documented one, pinned to the float64 slab oracle.
+ *   ncw_voxel_view_seen   : replaces kaolin_renderer.py:33-51 (gen_rays) + :110-141 (__call__) + generate_voxel.py:311-439
+ *                           (get_near_far, return_pts) + reproj_filter.py:224-225 for ONE view, pixels [p0, p0 + n) row-major,
+ *                           one lane per pixel.  view: HOST struct; pose = row-major 3x3 camera -> world part of
+ *                           inv(E inv(sfm2gt)) (OpenCV axes, scale included), o_norm = (camera centre + 1e-7 - box centre) /
+ *                           scale computed by the host in float64 (generate_voxel.py:333, :345).  Ray of pixel (row j, col i):
+ *                           dir = pose ((i - cx) / fx, (j - cy) / fy, 1), dir_norm = |dir|, d = dir / dir_norm + 1e-7 per
+ *                           component (:332); grid coordinates and depths as ncw_ray_voxel_near_far's.  The walk STOPS at the
+ *                           first occupied voxel in depth order; the ray is valid iff that voxel's entry depth is > 1e-4
+ *                           (:397-400: a camera inside an occupied voxel sees nothing along that ray).  grid: HOST struct
+ *                           (origin is not read; scale turns depths into the units of the box).  A valid ray sets its
+ *                           voxel's bit in seen (same layout and size as grid->occ; atomicOr, issued only when a plain load
+ *                           finds the bit clear: the grid only gains bits, so the result is order-independent and bitwise
+ *                           reproducible), voxel[p - p0] = (x G + y) G + z, depth[p - p0] = near scale / dir_norm + 0.02
+ *                           (kaolin_renderer.py:127, 141: camera-space z).  Any other ray sets nothing, voxel = -1, depth = 0
+ *                           (the reference's pid = -1 wraps round and marks an unrelated voxel, and its depth is 0.02: neither
+ *                           is reproduced).  seen is NOT cleared: views accumulate.  depth / voxel: optional planes [n]
+ *                           (NULL = not written).
+ *   ncw_voxel_points_seen : replaces kaolin_renderer.py:53-107 (get_index over vertex_table) for any target:
+ *                           flags[i] (uint8) = the bit in seen of the voxel of normalised point i (f32 [n,3]), the voxel
+ *                           computed with ncw_voxel_build's arithmetic ((p + 1) (0.5f G), truncated); 0 for a point outside
+ *                           the cube or NaN (:102, voxel_id = -10).
+ * Both return NCW_E_BADARG for NULL grid / seen pointers, a level outside 3..10 or a range outside the view; 0 without a
+ * launch for n == 0.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct NcwVoxelView {
+    float fx, fy, cx, cy;
+    float pose[9];
+    float o_norm[3];
+    int32_t width, height;
+} NcwVoxelView;
+
+int ncw_voxel_view_seen(const NcwVoxelView* view, const NcwCacheOctree* grid, int64_t p0, int64_t n, uint32_t* seen,
+                        float* depth, int32_t* voxel, void* stream);
+int ncw_voxel_points_seen(const float* pts_normalised, int64_t n, int level, const uint32_t* seen, uint8_t* flags,
+                          void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Area-weighted surface sampling of a triangle mesh (csrc/ncw_surf.hip) for the mesh evaluation: the open3d branch of the
  * reference scores a predicted MESH by 10 |GT| points drawn uniformly by area from the triangles inside the evaluation box
  * (utils/eval_utils.py:20-61: `mesh_pred.crop(bbox_gt)` :39, `sample_points_uniformly` :42) and colours the two clouds by

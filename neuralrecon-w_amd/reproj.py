@@ -9,7 +9,9 @@ every valid pixel and runs one open3d KD-tree query per pixel in a Python loop; 
   * back-projection and marking: ncw_raster_backproject / ncw_raster_mark, nearest neighbours by evalmesh.NNGrid (exact,
     ties to the smaller index);
   * COLMAP cameras.bin / images.bin and the tsv split read here (no pandas, no open3d, no trimesh); PINHOLE cameras only;
-  * one process, one GPU: the views are independent and run one after another.
+  * one process, one GPU: the views are independent and run one after another;
+  * a source WITHOUT faces (a point cloud: utils/reproj_filter.py:110-115, utils/kaolin_renderer.py) is voxelised over the
+    evaluation box (`VoxelCloud`) and every view is traced to the first occupied voxel by csrc/ncw_voxview.hip.
 """
 import csv
 import ctypes as C
@@ -379,28 +381,158 @@ class Target:
 
     def rows(self):
         """np.unique over the rows [xyz, rgb] of the marked vertices (lexicographic): (xyz float64, rgb uint8)."""
-        keep = torch.nonzero(self.flags[: self.m]).reshape(-1).cpu().numpy()
-        if keep.shape[0] == 0:
-            return np.zeros((0, 3)), np.zeros((0, 3), dtype=np.uint8)
-        rows = np.concatenate([self.xyz[keep], self.rgb[keep].astype(np.float64)], 1)
-        u = torch.unique(torch.from_numpy(rows).to(self.dev), dim=0).cpu().numpy()  # sorted rows, as np.unique(axis=0)
-        return u[:, :3].copy(), u[:, 3:].astype(np.uint8)
+        return unique_rows(self.xyz, self.rgb, self.flags[: self.m], self.dev)
+
+
+def unique_rows(xyz, rgb, flags, device):
+    """np.unique over the rows [xyz, rgb] of the vertices whose flag is set (lexicographic): (xyz float64, rgb uint8)."""
+    keep = torch.nonzero(flags).reshape(-1).cpu().numpy()
+    if keep.shape[0] == 0:
+        return np.zeros((0, 3)), np.zeros((0, 3), dtype=np.uint8)
+    rows = np.concatenate([xyz[keep], rgb[keep].astype(np.float64)], 1)
+    u = torch.unique(torch.from_numpy(rows).to(device), dim=0).cpu().numpy()  # sorted rows, as np.unique(axis=0)
+    return u[:, :3].copy(), u[:, 3:].astype(np.uint8)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the point-cloud source (utils/kaolin_renderer.py; csrc/ncw_voxview.hip)
+# ---------------------------------------------------------------------------------------------------
+def cloud_cube(scene_config, voxel_size):
+    """generate_voxel.py:104-118, 146 for gen_octree(..., expand=0, radius=1, in_sfm=False): the evaluation box `eval_bbx` AS
+    GIVEN (GT frame; its two corners are not sorted, as in the reference), origin = its centre, scale = longest edge / 2,
+    level = floor(log2(2 scale / voxel_size)).  Returns (origin float64 [3], scale, level).  ValueError for a config without
+    eval_bbx or a level outside the 3..10 of the bit grids."""
+    if not isinstance(scene_config, dict) or scene_config.get("eval_bbx") is None:
+        raise ValueError("the scene's config.yaml has no eval_bbx: a point-cloud source is voxelised over the evaluation box")
+    lo = np.array(scene_config["eval_bbx"][0], dtype=np.float64)
+    hi = np.array(scene_config["eval_bbx"][1], dtype=np.float64)
+    origin = lo + (hi - lo) / 2
+    scale = float(np.max(hi - lo) / 2)
+    if not (scale > 0 and float(voxel_size) > 0):
+        raise ValueError("eval_bbx %r / voxel_size %r span no volume" % (scene_config["eval_bbx"], voxel_size))
+    level = int(np.floor(np.log2(2 * scale / float(voxel_size))))
+    if level > 10:
+        raise ValueError("voxel_size %g gives octree level %d over this evaluation box (longest edge %g); the bit grid goes up to "
+                         "level 10: the smallest voxel_size that fits is above %.9g" % (voxel_size, level, 2 * scale, 2 * scale / 2048))
+    if level < 3:
+        raise ValueError("voxel_size %g gives octree level %d over this evaluation box (longest edge %g); the bit grid starts at "
+                         "level 3: the largest voxel_size that fits is %.9g" % (voxel_size, level, 2 * scale, 2 * scale / 8))
+    return origin, scale, level
+
+
+class VoxelCloud:
+    """utils/kaolin_renderer.py's renderer for a point-cloud source: gen_octree(data_path, points, voxel_size, expand=0,
+    in_sfm=False) (generate_voxel.py:75-150) as a bit-packed occupancy over the evaluation box (`cloud_cube`), and a `seen`
+    grid of the same layout that the views accumulate their first-hit voxels into.  points_gt: [N,3] in the frame of
+    eval_bbx (GT), normalised in float64 and then cast to f32; the occupied voxels are those ncw_voxel_build finds a point
+    in (a point outside the cube, or on its upper faces, has none)."""
+
+    def __init__(self, points_gt, scene_config, voxel_size, device=None):
+        dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        if dev.type != "cuda":
+            raise L.NeuconwHipError("reproj.VoxelCloud: the voxel views run on a GPU only; there is no CPU fallback")
+        if dev.index is None:  # 'cuda' -> the current device, so that tensors' devices compare equal to it
+            dev = torch.device("cuda", torch.cuda.current_device())
+        self.origin, self.scale, self.level = cloud_cube(scene_config, voxel_size)
+        self.dev = dev
+        self.voxel_size = float(voxel_size)
+        G = self.G = 1 << self.level
+        self.occ = torch.zeros(G * G * G // 32, dtype=torch.int32, device=dev)
+        self.brick = torch.zeros((max(G // 8, 1) ** 3 + 31) // 32, dtype=torch.int32, device=dev)
+        self.seen = torch.zeros_like(self.occ)
+        pn = self.normalise(points_gt)
+        L.check(L.get_lib().ncw_voxel_build(L.ptr(pn), int(pn.shape[0]), self.level, L.ptr(self.occ), L.ptr(self.brick),
+                                            L.stream_ptr(dev)), "ncw_voxel_build")
+        g = self.grid = L.NcwCacheOctree()
+        for a in range(3):
+            g.origin[a] = float(self.origin[a])
+        g.scale, g.level = self.scale, self.level
+        g.occ, g.brick = self.occ.data_ptr(), self.brick.data_ptr()
+
+    def normalise(self, points_gt):
+        """f32 [N,3] on the device: (points - origin) / scale in float64, then cast."""
+        p = points_gt.detach().cpu().numpy() if torch.is_tensor(points_gt) else points_gt
+        p = np.asarray(p, dtype=np.float64).reshape(-1, 3)
+        return torch.from_numpy(((p - self.origin) / self.scale).astype(np.float32)).to(self.dev).contiguous()
+
+    def view_struct(self, K, pose, height, width):
+        """NcwVoxelView of the camera K (3x3) at camera -> world `pose` (3x4 / 4x4, GT frame, scale included): the camera
+        centre is normalised to the cube in float64 (generate_voxel.py:333, :345), then everything is rounded to f32."""
+        K = np.asarray(K, dtype=np.float64)
+        P = np.asarray(pose, dtype=np.float64)[:3, :4]
+        s = L.NcwVoxelView()
+        s.fx, s.fy, s.cx, s.cy = float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
+        for i, x in enumerate(P[:, :3].reshape(-1)):
+            s.pose[i] = float(x)
+        for i, x in enumerate((P[:, 3] + 1e-7 - self.origin) / self.scale):
+            s.o_norm[i] = float(x)
+        s.width, s.height = int(width), int(height)
+        return s
+
+    def trace(self, K, pose, height, width, depth=None, voxel=None):
+        """One view, one launch, no host synchronisation: every pixel's first occupied voxel is marked in `seen`.  depth
+        (f32) / voxel (int32): optional contiguous device tensors of height * width elements that receive the planes."""
+        n = int(height) * int(width)
+        for t, dt in ((depth, torch.float32), (voxel, torch.int32)):
+            if t is not None and (t.dtype != dt or t.numel() != n or t.device != self.dev or not t.is_contiguous()):
+                raise ValueError("reproj.VoxelCloud.trace: planes are contiguous %d-element f32 (depth) / int32 (voxel) tensors on %s" % (n, self.dev))
+        s = self.view_struct(K, pose, height, width)
+        L.check(L.get_lib().ncw_voxel_view_seen(C.byref(s), C.byref(self.grid), 0, n, L.ptr(self.seen), L.ptr(depth), L.ptr(voxel),
+                                                L.stream_ptr(self.dev)), "ncw_voxel_view_seen")
+
+    def select(self, points_gt):
+        """bool [N] on the device: point i lies in a voxel of THIS grid that some traced pixel hit first."""
+        pn = self.normalise(points_gt)
+        n = int(pn.shape[0])
+        flags = torch.zeros(n, dtype=torch.uint8, device=self.dev)
+        if n == 0:
+            return flags.bool()
+        L.check(L.get_lib().ncw_voxel_points_seen(L.ptr(pn), n, self.level, L.ptr(self.seen), L.ptr(flags), L.stream_ptr(self.dev)),
+                "ncw_voxel_points_seen")
+        return flags.bool()
+
+    def clear(self):
+        self.seen.zero_()
+
+
+@torch.no_grad()
+def render_cloud_depth(points, scene_config, voxel_size, K, pose, height, width, device=None):
+    """The counterpart of `render_depth` for a point cloud (utils/kaolin_renderer.py:110-141): points [N,3] in the frame of
+    scene_config's eval_bbx, voxelised at voxel_size (`VoxelCloud`), seen by the pinhole camera K at camera -> world `pose`;
+    pixel (r, c) casts its ray through the INTEGER image point (c, r).  Returns (depth [H,W] f32: camera-space z of the entry
+    into the first occupied voxel + 0.02, 0 where nothing is hit or the camera stands inside that voxel; voxel [H,W] int32:
+    its linear index (x G + y) G + z, -1 there) on the device."""
+    cloud = VoxelCloud(points, scene_config, voxel_size, device)
+    depth = torch.empty(int(height) * int(width), dtype=torch.float32, device=cloud.dev)
+    voxel = torch.empty(int(height) * int(width), dtype=torch.int32, device=cloud.dev)
+    cloud.trace(K, pose, height, width, depth, voxel)
+    return depth.view(int(height), int(width)), voxel.view(int(height), int(width))
 
 
 @torch.no_grad()
 def reproj_filter(src_file, target_file, data_path, output_path, gt=False, voxel_size=0.01, visualize=False, znear=ZNEAR,
                   zfar=ZFAR, cull="back", device=None, verbose=True):
-    """utils/reproj_filter.py: keep the vertices of target_file that a training view of data_path sees on src_file's mesh.
-    Per view: render the depth of the source mesh, back-project every pixel with depth > 0 at its integer pixel coordinates,
-    mark the nearest target vertex when it is closer than 2 sqrt(2) voxel_size (GT units).  Both files are carried to GT
-    coordinates by config.yaml's sfm2gt unless `gt`.  Writes <output_path>/reprojected.ply (np.unique of the marked rows
+    """utils/reproj_filter.py: keep the vertices of target_file that a training view of data_path sees on src_file.
+    A source WITH faces (a mesh).  Per view: render the depth of the source mesh, back-project every pixel with depth > 0
+    at its integer pixel coordinates, mark the nearest target vertex when it is closer than 2 sqrt(2) voxel_size (GT units).
+    Both files are carried to GT coordinates by config.yaml's sfm2gt unless `gt`.  Writes <output_path>/reprojected.ply (np.unique of the marked rows
     [xyz, rgb], double xyz + uchar colours); `visualize` also writes render/depth/<name>.npy and render/reprojects/<name>.ply.
+    A source WITHOUT faces (a point cloud; :110-115, utils/kaolin_renderer.py).  Source and target go to GT coordinates; the
+    source is voxelised over config.yaml's eval_bbx at level floor(log2(longest edge / voxel_size)) (`VoxelCloud`); every
+    pixel of every view is traced to the first occupied voxel (csrc/ncw_voxview.hip).  A target vertex is kept iff the voxel
+    of the SOURCE's grid that contains it was the first hit of some training-view pixel (the reference indexes the target by
+    the source's point -> voxel table, which is this rule when the two files hold the same points -- its one use -- and is
+    undefined otherwise).  The nearest-neighbour marking and its 2 sqrt(2) voxel_size are not used on this path (:224-225);
+    znear / zfar / cull do not apply.  A pixel that misses marks nothing and has depth 0 (the reference's wrap-around of
+    pid = -1 and its depth of 0.02 there are not reproduced).
     Returns (xyz float64 [K,3], rgb uint8 [K,3])."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     log = print if verbose else (lambda *a, **k: None)
     os.makedirs(output_path, exist_ok=True)
     log("result will be saved to %s" % output_path)
-    S = read_sfm2gt(data_path)
+    with open(os.path.join(data_path, "config.yaml")) as fh:
+        scene_config = yaml.safe_load(fh)
+    S = np.array(scene_config["sfm2gt"], dtype=np.float64)
     views = load_views(data_path, S)
     log("views to process: %d" % len(views))
 
@@ -409,11 +541,16 @@ def reproj_filter(src_file, target_file, data_path, output_path, gt=False, voxel
         t_xyz = evalmesh.apply_transform(t_xyz, S)
     if t_rgb is None:
         log("No color found in target point cloud")
-    target = Target(t_xyz, t_rgb, 2 * np.sqrt(2) * voxel_size, dev)
 
     s_verts, s_faces, _ = read_ply_mesh(src_file)
     if s_faces.shape[0] == 0:
-        raise ValueError("%s has no faces: the point-cloud source (the reference's kaolin renderer) is not supported" % src_file)
+        log("reproject point cloud")
+        xyz, rgb = _filter_cloud(s_verts if gt else evalmesh.apply_transform(s_verts, S), t_xyz, t_rgb, views, scene_config,
+                                 output_path, voxel_size, visualize, dev)
+        write_ply_points(os.path.join(output_path, "reprojected.ply"), xyz, rgb)
+        log("kept %d of %d vertices" % (xyz.shape[0], t_xyz.shape[0]))
+        return xyz, rgb
+    target = Target(t_xyz, t_rgb, 2 * np.sqrt(2) * voxel_size, dev)
     mesh = RasterMesh(s_verts, s_faces, dev)
     zbuf = None
     for v in views:
@@ -440,6 +577,30 @@ def reproj_filter(src_file, target_file, data_path, output_path, gt=False, voxel
     write_ply_points(os.path.join(output_path, "reprojected.ply"), xyz, rgb)
     log("kept %d of %d vertices" % (xyz.shape[0], target.m))
     return xyz, rgb
+
+
+def _filter_cloud(s_xyz, t_xyz, t_rgb, views, scene_config, output_path, voxel_size, visualize, dev):
+    """The point-cloud source of reproj_filter (source and target already in GT coordinates; scene_config: the parsed
+    config.yaml): one trace per view with the pose inv(E inv(sfm2gt)), one select over the target at the end; the unique
+    rows of the kept vertices."""
+    cloud = VoxelCloud(s_xyz, scene_config, voxel_size, dev)
+    depth = None
+    for v in views:
+        w, h = v["wh"]
+        if visualize and (depth is None or depth.numel() != h * w):
+            depth = torch.empty(h * w, dtype=torch.float32, device=dev)
+        cloud.trace(v["K"], v["pose"], h, w, depth=depth if visualize else None)
+        if visualize:
+            stem = os.path.splitext(v["name"])[0]
+            for sub in ("depth", "reprojects"):
+                os.makedirs(os.path.join(output_path, "render", sub), exist_ok=True)
+            np.save(os.path.join(output_path, "render", "depth", stem + ".npy"), depth.view(h, w).cpu().numpy())
+            pts, _ = backproject(depth.view(h, w), backproject_matrix(v["K"], v["pose"], cloud.origin))
+            write_ply_points(os.path.join(output_path, "render", "reprojects", stem + ".ply"),
+                             pts.double().cpu().numpy() + cloud.origin)
+    t_xyz = np.ascontiguousarray(t_xyz, dtype=np.float64).reshape(-1, 3)
+    rgb = np.zeros(t_xyz.shape, dtype=np.uint8) if t_rgb is None else np.asarray(t_rgb, dtype=np.uint8).reshape(-1, 3)
+    return unique_rows(t_xyz, rgb, cloud.select(t_xyz), dev)
 
 
 # ---------------------------------------------------------------------------------------------------

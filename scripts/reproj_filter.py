@@ -6,6 +6,8 @@ open3d, trimesh or ray -- keeps the vertices of --target_file that some training
         --target_file results/.../mesh/extracted_mesh_level_10_colored.ply \
         --data_path data/heritage-recon/brandenburg_gate --output_path results/.../mesh
 
+  * a --src_file without faces is a point cloud: it is voxelised over the scene's eval_bbx at --voxel_size and every view is
+    traced to the first occupied voxel; a target vertex is kept iff its voxel was some pixel's first hit (INTEGRATION.md);
   * writes <output_path>/reprojected.ply (double x / y / z, uchar colours), in GT coordinates;
   * --visualize writes render/depth/<name>.npy and render/reprojects/<name>.ply (the reference writes JPEGs);
   * --n_cpus / --n_gpus are accepted for compatibility and ignored: one process renders every view on one GPU.
@@ -20,7 +22,7 @@ from neuralrecon_w_amd import reproj  # noqa: E402
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description="reprojection visibility filter (GPU)")
-    ap.add_argument("--src_file", type=str, required=True, help="mesh file path")
+    ap.add_argument("--src_file", type=str, required=True, help="mesh file path, or a point cloud (no faces)")
     ap.add_argument("--target_file", type=str, default=None, help="point cloud to be filtered (default: --src_file)")
     ap.add_argument("--data_path", type=str, required=True, help="camera poses in colmap format")
     ap.add_argument("--output_path", type=str, required=True, help="output path")
