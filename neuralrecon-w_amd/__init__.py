@@ -3,16 +3,23 @@
 Drop-in for the reference's `models.neuconw.NeuconW`, `models.nerf.NeRF` and
 `rendering.renderer.NeuconWRenderer`.  All per-sample compute is in
 libneuconw_hip.so (hand-written HIP, C ABI in include/neuconw_hip.h).
+
+The names below are bound on first use (PEP 562), not at import time, so that the file readers (`colmap`, `ply`) import without
+torch.  `import neuralrecon_w_amd` alone therefore loads nothing: a missing module or library shows at the first name used.
 """
-from . import lib  # noqa: F401
-from . import mesh  # noqa: F401
-from . import evalmesh  # noqa: F401
-from . import reproj  # noqa: F401
-from . import views  # noqa: F401
-from .lib import PREC_BF16, PREC_F16, PREC_F32, NeuconwHipError  # noqa: F401
-from .nerf import NeRF  # noqa: F401
-from .neuconw import NeuconW, RenderingNetwork, SDFNetwork, SingleVarianceNetwork  # noqa: F401
-from .renderer import NeuconWRenderer  # noqa: F401
-from .losses import NeuconWLoss  # noqa: F401
-from .trainer import FlatAdam, FlatParams, TrainStep  # noqa: F401
-from .views import Camera, render_view, scene_view, write_panel  # noqa: F401
+import importlib
+
+_SUBMODULES = ("lib", "mesh", "evalmesh", "reproj", "views")
+_HOME = {"PREC_BF16": "lib", "PREC_F16": "lib", "PREC_F32": "lib", "NeuconwHipError": "lib", "NeRF": "nerf", "NeuconW": "neuconw",
+         "RenderingNetwork": "neuconw", "SDFNetwork": "neuconw", "SingleVarianceNetwork": "neuconw", "NeuconWRenderer": "renderer",
+         "NeuconWLoss": "losses", "FlatAdam": "trainer", "FlatParams": "trainer", "TrainStep": "trainer", "Camera": "views",
+         "render_view": "views", "scene_view": "views", "write_panel": "views"}
+
+
+def __getattr__(name):
+    if name in _SUBMODULES:
+        return importlib.import_module("." + name, __name__)
+    if name in _HOME:
+        value = globals()[name] = getattr(importlib.import_module("." + _HOME[name], __name__), name)
+        return value
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -21,62 +21,26 @@ from seeded generators, same lengths and semantics).  Only npz output; h5 is ref
 import ctypes as C
 import json
 import os
-import struct
 import time
 
 import numpy as np
 import torch
 
 from . import lib as L
-from . import views, voxel
+from . import colmap, views, voxel
 
 # datasets/phototourism.py:81-92: the share of rays with a key-point depth each image is padded up to
 DEPTH_PERCENT = {"brandenburg_gate": 0.2, "palacio_de_bellas_artes": 0.4}
 
 
 # ---------------------------------------------------------------------------------------------------
-# COLMAP readers: what the cache needs beyond views.read_scene
+# the SfM points as the dataset holds them
 # ---------------------------------------------------------------------------------------------------
-def read_image_points(path):
-    """The 2-D points of COLMAP `images.bin` that reproj.read_images_binary skips: {image_id: (xys float64 [n,2],
-    point3D_ids int64 [n])}, file order (utils/colmap_utils.py:214-247; -1 = no 3-D point)."""
-    out = {}
-    with open(path, "rb") as fh:
-        buf = fh.read()
-    (n,) = struct.unpack_from("<Q", buf, 0)
-    off = 8
-    rec = np.dtype([("x", "<f8"), ("y", "<f8"), ("id", "<i8")])
-    for _ in range(n):
-        (iid,) = struct.unpack_from("<i", buf, off)
-        off = buf.index(b"\x00", off + 64) + 1
-        (n2d,) = struct.unpack_from("<Q", buf, off)
-        off += 8
-        pts = np.frombuffer(buf, dtype=rec, count=n2d, offset=off)
-        off += 24 * n2d
-        out[iid] = (np.stack([pts["x"], pts["y"]], -1).astype(np.float64).reshape(-1, 2), pts["id"].astype(np.int64))
-    if off != len(buf):
-        raise ValueError("%s: %d trailing bytes after %d images (not a COLMAP images.bin?)" % (path, len(buf) - off, n))
-    return out
-
-
 def read_points3d_table(path):
     """COLMAP `points3D.bin` by point id, as phototourism.py:530-534 holds it: (xyz float32 [max_id + 1, 3], error float32
     [max_id + 1]); rows of ids the file does not list are ones, as `torch.ones` leaves them there."""
-    with open(path, "rb") as fh:
-        buf = fh.read()
-    (n,) = struct.unpack_from("<Q", buf, 0)
-    off = 8
-    ids = np.empty(n, dtype=np.int64)
-    xyz = np.empty((n, 3), dtype=np.float64)
-    err = np.empty(n, dtype=np.float64)
-    for i in range(n):
-        ids[i], xyz[i, 0], xyz[i, 1], xyz[i, 2] = struct.unpack_from("<Qddd", buf, off)
-        (err[i],) = struct.unpack_from("<d", buf, off + 35)
-        (track,) = struct.unpack_from("<Q", buf, off + 43)
-        off += 51 + 8 * int(track)
-    if off != len(buf):
-        raise ValueError("%s: %d trailing bytes after %d points (not a COLMAP points3D.bin?)" % (path, len(buf) - off, n))
-    size = int(ids.max()) + 1 if n else 1
+    ids, xyz, err, _ = colmap.read_points3d(path)
+    size = int(ids.max()) + 1 if len(ids) else 1
     xyz_t = np.ones((size, 3), dtype=np.float32)
     err_t = np.ones(size, dtype=np.float32)
     xyz_t[ids] = xyz.astype(np.float32)
@@ -351,10 +315,9 @@ def build_cache(root_dir, cache_dir="cache", img_downscale=1, semantic_map_path=
     if device.type != "cuda":
         raise L.NeuconwHipError("cachebuild.build_cache: not a GPU device; the ray cache has no CPU fallback")
     root_dir = os.path.normpath(root_dir)
-    scene = views.read_scene(root_dir, sfm_path)
+    scene = views.read_scene(root_dir, sfm_path, with_points=True)
     if depth_percent is None:
         depth_percent = DEPTH_PERCENT.get(os.path.basename(root_dir), 0.0)
-    points2d = read_image_points(os.path.join(scene["sp"], "images.bin"))
     xyz_table, err_table = read_points3d_table(os.path.join(scene["sp"], "points3D.bin"))
     hit = rng = None
     voxel_size = 0.0
@@ -379,8 +342,8 @@ def build_cache(root_dir, cache_dir="cache", img_downscale=1, semantic_map_path=
         K, w2c, c2w, _, _ = views.image_pose(scene, image_id, img_downscale)
         near, far = views.image_near_far(scene, w2c, scene_origin, scene_radius)
         cam = views.Camera(K, c2w, w, h, near, far)
-        xys, p3d = points2d[image_id]
-        kp = image_keypoints(xys, p3d, xyz_table, err_table, w, h, img_downscale)
+        im = scene["images"][image_id]
+        kp = image_keypoints(im["xys"], im["point3d_ids"], xyz_table, err_table, w, h, img_downscale)
         rays, rgbs = build_image(cam, img, image_id, kp, w2c, lab, hit, rng, voxel_size, depth_percent, gen, device)
         all_rays.append(rays.cpu())
         all_rgbs.append(rgbs.cpu())

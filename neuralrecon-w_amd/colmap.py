@@ -1,0 +1,114 @@
+"""The scene files every tool at the edge of the renderer reads: a COLMAP binary model (cameras.bin, images.bin, points3D.bin;
+utils/colmap_utils.py) and the tsv split file of a scene directory.  One parser per format; numpy and the standard library only,
+so that reading a scene needs neither torch nor the HIP library.
+"""
+import csv
+import glob
+import os
+import struct
+
+import numpy as np
+
+# COLMAP camera models: id -> (name, number of parameters)
+CAMERA_MODELS = {0: ("SIMPLE_PINHOLE", 3), 1: ("PINHOLE", 4), 2: ("SIMPLE_RADIAL", 4), 3: ("RADIAL", 5), 4: ("OPENCV", 8),
+                 5: ("OPENCV_FISHEYE", 8), 6: ("FULL_OPENCV", 12), 7: ("FOV", 5), 8: ("SIMPLE_RADIAL_FISHEYE", 4),
+                 9: ("RADIAL_FISHEYE", 5), 10: ("THIN_PRISM_FISHEYE", 12)}
+PINHOLE = 1
+
+
+def read_cameras(path):
+    """COLMAP cameras.bin: {camera_id: dict(id, model, width, height, params float64)}.  Layout (little-endian): uint64
+    count, then per camera int32 id, int32 model id, uint64 width, uint64 height, float64 params[n(model)].  Only PINHOLE
+    cameras (fx, fy, cx, cy) are accepted: any other model is refused with a ValueError (the reference would read the
+    first four parameters of any model as fx, fy, cx, cy)."""
+    cams = {}
+    with open(path, "rb") as fh:
+        (n,) = struct.unpack("<Q", fh.read(8))
+        for _ in range(n):
+            cid, model, width, height = struct.unpack("<iiQQ", fh.read(24))
+            if model != PINHOLE:
+                name = CAMERA_MODELS.get(model, ("unknown model id %d" % model,))[0]
+                raise ValueError("%s: camera %d is %s; only PINHOLE cameras (undistorted images) are supported" % (path, cid, name))
+            params = np.frombuffer(fh.read(8 * 4), dtype="<f8").astype(np.float64)
+            cams[cid] = {"id": cid, "model": model, "width": int(width), "height": int(height), "params": params}
+    return cams
+
+
+def read_images(path, with_points=False):
+    """COLMAP images.bin: {image_id: dict(id, qvec, tvec, camera_id, name)}, file order.  Layout: uint64 count, then per image
+    int32 id, float64 qvec[4] (w, x, y, z), float64 tvec[3], int32 camera id, the name as NUL-terminated UTF-8 bytes, uint64 n2d,
+    n2d x (float64 x, float64 y, int64 point3D id; -1 = no 3-D point).  with_points: every dict also carries the 2-D points,
+    `xys` float64 [n2d, 2] and `point3d_ids` int64 [n2d] (utils/colmap_utils.py:214-247).  A file that ends early or goes on after
+    its last image is refused with a ValueError."""
+    with open(path, "rb") as fh:
+        buf = fh.read()
+    (n,) = struct.unpack_from("<Q", buf, 0)
+
+    def short(k):
+        return ValueError("%s: the file ends inside image %d of %d (not a COLMAP images.bin?)" % (path, k + 1, n))
+
+    pt = np.dtype([("x", "<f8"), ("y", "<f8"), ("id", "<i8")])
+    imgs = {}
+    off = 8
+    for k in range(n):
+        try:
+            rec = struct.unpack_from("<i7di", buf, off)
+            end = buf.index(b"\x00", off + 64)
+            (n2d,) = struct.unpack_from("<Q", buf, end + 1)
+        except (struct.error, ValueError):
+            raise short(k) from None
+        name = buf[off + 64:end].decode("utf-8")
+        off = end + 9
+        if off + 24 * n2d > len(buf):
+            raise short(k)
+        im = {"id": rec[0], "qvec": np.array(rec[1:5]), "tvec": np.array(rec[5:8]), "camera_id": rec[8], "name": name}
+        if with_points:
+            pts = np.frombuffer(buf, dtype=pt, count=n2d, offset=off)
+            im["xys"] = np.stack([pts["x"], pts["y"]], -1).astype(np.float64).reshape(-1, 2)
+            im["point3d_ids"] = pts["id"].astype(np.int64)
+        imgs[rec[0]] = im
+        off += 24 * n2d
+    if off != len(buf):
+        raise ValueError("%s: %d trailing bytes after %d images (not a COLMAP images.bin?)" % (path, len(buf) - off, n))
+    return imgs
+
+
+def read_points3d(path):
+    """COLMAP points3D.bin (utils/colmap_utils.py:264-291: uint64 count, then per point `<QdddBBBd` + uint64 track length + that
+    many `<ii` track elements) -> (ids int64 [N], xyz float64 [N,3], reprojection error float64 [N], track length int64 [N]),
+    file order.  The one walk of the file: voxel.read_points3d_xyz, evalmesh.read_points3d_filtered and
+    cachebuild.read_points3d_table are views of what it returns."""
+    with open(path, "rb") as fh:
+        buf = fh.read()
+    (n,) = struct.unpack_from("<Q", buf, 0)
+    off = 8
+    ids = np.empty(n, dtype=np.int64)
+    xyz = np.empty((n, 3), dtype=np.float64)
+    err = np.empty(n, dtype=np.float64)
+    track = np.empty(n, dtype=np.int64)
+    for i in range(n):
+        ids[i], xyz[i, 0], xyz[i, 1], xyz[i, 2] = struct.unpack_from("<Qddd", buf, off)
+        (err[i],) = struct.unpack_from("<d", buf, off + 35)
+        (track[i],) = struct.unpack_from("<Q", buf, off + 43)
+        off += 51 + 8 * int(track[i])
+    if off != len(buf):
+        raise ValueError("%s: %d trailing bytes after %d points (not a COLMAP points3D.bin?)" % (path, len(buf) - off, n))
+    return ids, xyz, err, track
+
+
+def qvec2rotmat(q):
+    """Rotation of the unit quaternion (w, x, y, z) (COLMAP's convention: world -> camera)."""
+    w, x, y, z = [float(v) for v in q]
+    return np.array([[1 - 2 * y * y - 2 * z * z, 2 * x * y - 2 * w * z, 2 * z * x + 2 * w * y],
+                     [2 * x * y + 2 * w * z, 1 - 2 * x * x - 2 * z * z, 2 * y * z - 2 * w * x],
+                     [2 * z * x - 2 * w * y, 2 * y * z + 2 * w * x, 1 - 2 * x * x - 2 * y * y]])
+
+
+def split_rows(root_dir):
+    """(path, rows) of the scene's split file: the first <root_dir>/*.tsv sorted by name and its rows as dicts, file order.
+    FileNotFoundError without one.  Which rows count is the caller's rule (reproj.read_train_split, views.read_scene)."""
+    tsvs = sorted(glob.glob(os.path.join(root_dir, "*.tsv")))
+    if not tsvs:
+        raise FileNotFoundError("no *.tsv split file in %s" % root_dir)
+    with open(tsvs[0], newline="") as fh:
+        return tsvs[0], list(csv.DictReader(fh, delimiter="\t"))

@@ -63,13 +63,6 @@ __global__ __launch_bounds__(CB) void splat_write_kernel(const float* __restrict
 // ---------------------------------------------------------------------------------------------
 // cache rows
 // ---------------------------------------------------------------------------------------------
-struct Octree {
-    float ox, oy, oz, scale;
-    int level;
-    const uint32_t* occ;
-    const uint32_t* brick;
-};
-
 struct RowArgs {
     NcwViewCamera cam;
     const uint8_t* image;   // [h, w, 3]
@@ -79,7 +72,7 @@ struct RowArgs {
     const float* weight;    // [h * w]
     float ts, voxel_size;
     int use_voxel;
-    Octree hit, range;
+    NcwCacheOctree hit, range;
     int64_t p0, n;
     int ncols;
     float* rows;
@@ -108,12 +101,11 @@ __global__ __launch_bounds__(CB) void cache_rows_kernel(RowArgs a) {
         if (a.use_voxel) {
             // phototourism.py:638-657: the hit octree decides which rays stay, the range octree gives their near / far
             float hn, hf;
-            ray_voxel_near_far(o, dn, a.hit.ox, a.hit.oy, a.hit.oz, a.hit.scale, a.hit.level, a.hit.occ, a.hit.brick, hn, hf);
+            ray_voxel_near_far(o, dn, a.hit, hn, hf);
             kept = hn > 0.f;
             if (kept) {
                 float rn, rf;
-                ray_voxel_near_far(o, dn, a.range.ox, a.range.oy, a.range.oz, a.range.scale, a.range.level, a.range.occ,
-                                   a.range.brick, rn, rf);
+                ray_voxel_near_far(o, dn, a.range, rn, rf);
                 near = rn;                                  // 0 / 0 where the range octree misses (:653-654)
                 far = rn > 0.f ? rf + a.voxel_size : rf;    // :305-308
             }
@@ -169,9 +161,6 @@ inline bool grid_fits(int64_t n) { return (n + CB - 1) / CB <= 0x7fffffffLL; }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 inline bool octree_ok(const NcwCacheOctree* t) { return t->occ != nullptr && t->brick != nullptr && t->level >= 3 && t->level <= 10 && t->scale > 0.f; }
-inline Octree octree_of(const NcwCacheOctree* t) {
-    return Octree{t->origin[0], t->origin[1], t->origin[2], t->scale, t->level, t->occ, t->brick};
-}
 
 }  // namespace
 
@@ -223,8 +212,8 @@ extern "C" int ncw_cache_rows(const NcwViewCamera* cam, const uint8_t* image, co
     a.ts = (float)image_id;  // id_ * torch.ones(...) (phototourism.py:562)
     a.voxel_size = voxel_size;
     a.use_voxel = (hit != nullptr && range != nullptr) ? 1 : 0;  // either octree missing: use_voxel = False
-    a.hit = a.use_voxel ? octree_of(hit) : Octree{};
-    a.range = a.use_voxel ? octree_of(range) : Octree{};
+    a.hit = a.use_voxel ? *hit : NcwCacheOctree{};
+    a.range = a.use_voxel ? *range : NcwCacheOctree{};
     a.p0 = p0;
     a.n = n;
     a.ncols = ncols;

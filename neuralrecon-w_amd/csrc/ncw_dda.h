@@ -1,11 +1,26 @@
 // The octree walk every ray / sparse-voxel kernel shares (ncw_voxel.hip: near-far and the nugget trace; ncw_cache.hip: the ray-cache
-// rows): the 3-D DDA over the bit-packed occupancy of voxel.py (x index slowest, 8^3-voxel brick mask for empty-space skipping) and
-// get_near_far's per-ray rule on top of it (tools/prepare_data/generate_voxel.py:311-439).
+// rows; ncw_voxview.hip: the first-hit views): the 3-D DDA over the bit-packed occupancy of voxel.py (x index slowest, 8^3-voxel
+// brick mask for empty-space skipping) and get_near_far's per-ray rule on top of it
+// (tools/prepare_data/generate_voxel.py:311-439).
 #pragma once
+#include "../../include/neuconw_hip.h"
 #include "ncw_common.h"
 
-// The 3-D DDA both ray kernels share: walks the level-`level` voxels a ray crosses inside the cube, in depth order, and calls
-// hit(t_entry, t_exit, linear voxel index) for every OCCUPIED one.  u = origin in grid coordinates, du = direction per unit depth.
+// The voxel of a point of the normalised cube: c = its integer coordinates at grid side G ((p + 1) (0.5f G), truncated); false for
+// a point outside the cube (or NaN).  ncw_voxel_build and ncw_voxel_points_seen must agree on it to the bit: both call this.
+__device__ __forceinline__ bool voxel_of_point(const float* p, int G, int (&c)[3]) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+        const float u = (p[a] + 1.0f) * (0.5f * (float)G);
+        if (!(u >= 0.f) || u >= (float)G) return false;
+        c[a] = (int)u;
+    }
+    return true;
+}
+
+// The 3-D DDA every ray kernel shares: walks the level-`level` voxels a ray crosses inside the cube, in depth order, and calls
+// hit(t_entry, t_exit, linear voxel index) for every OCCUPIED one; hit returns true to end the walk there (the first-hit views of
+// ncw_voxview.hip), false to go on.  u = origin in grid coordinates, du = direction per unit depth.
 template <class F>
 __device__ __forceinline__ void dda_walk(const float (&u)[3], const float (&du)[3], int G, const uint32_t* __restrict__ occ,
                                          const uint32_t* __restrict__ brick, F&& hit) {
@@ -50,7 +65,7 @@ __device__ __forceinline__ void dda_walk(const float (&u)[3], const float (&du)[
         }
         if (brick_on) {
             const int64_t v = ((int64_t)idx[0] * G + idx[1]) * G + idx[2];
-            if ((occ[v >> 5] >> (v & 31)) & 1u) hit(t_entry, tmax[ax], (int)v);
+            if (((occ[v >> 5] >> (v & 31)) & 1u) && hit(t_entry, tmax[ax], (int)v)) break;  // v < 2^30 at level 10
         }
         // advance to the next voxel along the ray
         t_entry = tmax[ax];
@@ -61,27 +76,27 @@ __device__ __forceinline__ void dda_walk(const float (&u)[3], const float (&du)[
     }
 }
 
-// get_near_far for ONE ray (o, d in SfM space; the cube is org +- scale): entry depth of the first and of the last occupied voxel in
-// SfM units, 0 / 0 where the ray misses.
-__device__ __forceinline__ void ray_voxel_near_far(const float (&ro)[3], const float (&rd)[3], float ox, float oy, float oz,
-                                                   float scale, int level, const uint32_t* __restrict__ occ,
-                                                   const uint32_t* __restrict__ brick, float& near_out, float& far_out) {
-    const int G = 1 << level;
+// get_near_far for ONE ray (o, d in SfM space; the cube is t.origin +- t.scale): entry depth of the first and of the last occupied
+// voxel in SfM units, 0 / 0 where the ray misses.
+__device__ __forceinline__ void ray_voxel_near_far(const float (&ro)[3], const float (&rd)[3], const NcwCacheOctree& t,
+                                                   float& near_out, float& far_out) {
+    const int G = 1 << t.level;
     const float half = 0.5f * (float)G;
-    const float org[3] = {ox, oy, oz};
+    const float scale = t.scale;
     float u[3], du[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         const float d = rd[a] + 1e-7f;            // generate_voxel.py:332
-        const float o = (ro[a] + 1e-7f - org[a]) / scale;  // :333, :345
+        const float o = (ro[a] + 1e-7f - t.origin[a]) / scale;  // :333, :345
         u[a] = (o + 1.0f) * half;   // grid coordinates
         du[a] = d * half;           // per unit of depth (depth is along the un-normalised direction)
     }
     float near = 0.f, far = 0.f;
     bool found = false;
-    dda_walk(u, du, G, occ, brick, [&](float t_in, float, int) {
+    dda_walk(u, du, G, t.occ, t.brick, [&](float t_in, float, int) {
         if (!found) { near = t_in; found = true; }
         far = t_in;
+        return false;
     });
     const bool valid = found && near > 1e-4f;  // generate_voxel.py:397
     near_out = valid ? near * scale : 0.f;  // :436-439

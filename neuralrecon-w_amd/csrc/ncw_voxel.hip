@@ -18,12 +18,7 @@ __global__ void voxel_build_kernel(const float* __restrict__ pts, int64_t n, int
     if (i >= n) return;
     const int G = 1 << level;
     int c[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float u = (pts[i * 3 + a] + 1.0f) * (0.5f * (float)G);
-        if (!(u >= 0.f) || u >= (float)G) return;  // outside the cube (or NaN)
-        c[a] = (int)u;
-    }
+    if (!voxel_of_point(pts + i * 3, G, c)) return;
     const int64_t v = ((int64_t)c[0] * G + c[1]) * G + c[2];
     atomicOr(&occ[v >> 5], 1u << (v & 31));
     const int Gb = G >> 3 > 0 ? G >> 3 : 1;
@@ -31,15 +26,13 @@ __global__ void voxel_build_kernel(const float* __restrict__ pts, int64_t n, int
     atomicOr(&brick[b >> 5], 1u << (b & 31));
 }
 
-__global__ void ray_voxel_kernel(const float* __restrict__ rays_o, const float* __restrict__ rays_d, int R,
-                                 float ox, float oy, float oz, float scale, int level,
-                                 const uint32_t* __restrict__ occ, const uint32_t* __restrict__ brick,
+__global__ void ray_voxel_kernel(const float* __restrict__ rays_o, const float* __restrict__ rays_d, int R, NcwCacheOctree tree,
                                  float* __restrict__ near_out, float* __restrict__ far_out) {
     const int r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= R) return;
     const float ro[3] = {rays_o[r * 3], rays_o[r * 3 + 1], rays_o[r * 3 + 2]};
     const float rd[3] = {rays_d[r * 3], rays_d[r * 3 + 1], rays_d[r * 3 + 2]};
-    ray_voxel_near_far(ro, rd, ox, oy, oz, scale, level, occ, brick, near_out[r], far_out[r]);
+    ray_voxel_near_far(ro, rd, tree, near_out[r], far_out[r]);
 }
 
 // kaolin.render.spc.unbatched_raytrace's contract (generate_voxel.py:358-368 is its one call site): EVERY (ray, occupied voxel)
@@ -63,7 +56,7 @@ __global__ void ray_voxel_trace_kernel(const float* __restrict__ rays_o, const f
     }
     if (!offsets) {
         int n = 0;
-        dda_walk(u, du, G, occ, brick, [&](float, float, int) { ++n; });
+        dda_walk(u, du, G, occ, brick, [&](float, float, int) { ++n; return false; });
         counts[r] = n;
     } else {
         int64_t at = offsets[r];
@@ -73,6 +66,7 @@ __global__ void ray_voxel_trace_kernel(const float* __restrict__ rays_o, const f
             nug_depth[2 * at] = t_in;
             nug_depth[2 * at + 1] = t_out;
             ++at;
+            return false;
         });
     }
 }
@@ -92,9 +86,9 @@ extern "C" int ncw_ray_voxel_near_far(const float* rays_o_sfm, const float* rays
                                       float* far_sfm, void* stream) {
     if (R <= 0) return 0;
     if (level < 3 || level > 10 || !scene_origin_host) return NCW_E_BADARG;
-    hipLaunchKernelGGL(ray_voxel_kernel, dim3((R + 63) / 64), dim3(64), 0, (hipStream_t)stream, rays_o_sfm, rays_d, R,
-                       scene_origin_host[0], scene_origin_host[1], scene_origin_host[2], scale, level, occ, brick, near_sfm,
-                       far_sfm);
+    const NcwCacheOctree tree = {{scene_origin_host[0], scene_origin_host[1], scene_origin_host[2]}, scale, level, 0, occ, brick};
+    hipLaunchKernelGGL(ray_voxel_kernel, dim3((R + 63) / 64), dim3(64), 0, (hipStream_t)stream, rays_o_sfm, rays_d, R, tree,
+                       near_sfm, far_sfm);
     NCW_CHECK_LAUNCH();
     return 0;
 }

@@ -8,63 +8,7 @@
 // the float64 slab oracle (oracle.ray_voxel_nuggets).
 #include "../../include/neuconw_hip.h"
 #include "ncw_common.h"
-
-// dda_walk (ncw_dda.h) with a stop: the same cube clip, start voxel and per-step arithmetic (the exit depth of a voxel comes from
-// its index, never accumulated), but the walk ends at the first OCCUPIED voxel.  Returns true and (t_in, v) of that voxel, false
-// when the ray leaves the cube first.  u = origin in grid coordinates, du = direction per unit depth.
-__device__ __forceinline__ bool dda_first(const float (&u)[3], const float (&du)[3], int G, const uint32_t* __restrict__ occ,
-                                          const uint32_t* __restrict__ brick, float& t_in, int& v_out) {
-    const int Gb = G >> 3 > 0 ? G >> 3 : 1;
-    float t0 = -3.0e38f, t1 = 3.0e38f;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float ta = (0.f - u[a]) / du[a], tb = ((float)G - u[a]) / du[a];
-        t0 = fmaxf(t0, fminf(ta, tb));
-        t1 = fminf(t1, fmaxf(ta, tb));
-    }
-    if (!(t1 >= fmaxf(t0, 0.f))) return false;
-    float t_entry = fmaxf(t0, 0.f);
-    int idx[3], step[3];
-    float tmax[3], inv[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float pos = u[a] + du[a] * t_entry;
-        int i = (int)floorf(pos);
-        // a ray entering through a face sits exactly on the boundary: step into the cube
-        if (du[a] > 0.f) i = min(max(i, 0), G - 1);
-        else i = min(max((int)ceilf(pos) - 1, 0), G - 1);
-        idx[a] = i;
-        step[a] = du[a] > 0.f ? 1 : -1;
-        inv[a] = 1.0f / du[a];
-        tmax[a] = ((float)(i + (du[a] > 0.f ? 1 : 0)) - u[a]) * inv[a];
-    }
-    int cur_brick = -1;
-    bool brick_on = false;
-    for (int it = 0; it < 3 * G + 3; ++it) {
-        int ax = 0;
-        if (tmax[1] < tmax[ax]) ax = 1;
-        if (tmax[2] < tmax[ax]) ax = 2;
-        const int b = ((idx[0] >> 3) * Gb + (idx[1] >> 3)) * Gb + (idx[2] >> 3);
-        if (b != cur_brick) {
-            cur_brick = b;
-            brick_on = (brick[b >> 5] >> (b & 31)) & 1u;
-        }
-        if (brick_on) {
-            const int64_t v = ((int64_t)idx[0] * G + idx[1]) * G + idx[2];  // < 2^30 at level 10
-            if ((occ[v >> 5] >> (v & 31)) & 1u) {
-                t_in = t_entry;
-                v_out = (int)v;
-                return true;
-            }
-        }
-        t_entry = tmax[ax];
-        if (ax == 0) { idx[0] += step[0]; tmax[0] = ((float)(idx[0] + (step[0] > 0 ? 1 : 0)) - u[0]) * inv[0]; }
-        else if (ax == 1) { idx[1] += step[1]; tmax[1] = ((float)(idx[1] + (step[1] > 0 ? 1 : 0)) - u[1]) * inv[1]; }
-        else { idx[2] += step[2]; tmax[2] = ((float)(idx[2] + (step[2] > 0 ? 1 : 0)) - u[2]) * inv[2]; }
-        if (idx[0] < 0 || idx[0] >= G || idx[1] < 0 || idx[1] >= G || idx[2] < 0 || idx[2] >= G) break;
-    }
-    return false;
-}
+#include "ncw_dda.h"
 
 // One lane per pixel of [p0, p0 + n), row-major.  A wave covers 64 neighbouring pixels of a row: their rays start together and
 // mostly end in the same few words of the grid, so the loads of occ / brick coalesce early in the walk and the bit is usually
@@ -93,7 +37,12 @@ __global__ void voxel_view_seen_kernel(NcwVoxelView cam, int level, float scale,
     }
     float near = 0.f;
     int v = -1;
-    const bool found = dda_first(u, du, G, occ, brick, near, v);
+    dda_walk(u, du, G, occ, brick, [&](float t_in, float, int vox) {  // the first occupied voxel ends the walk
+        near = t_in;
+        v = vox;
+        return true;
+    });
+    const bool found = v >= 0;
     const bool valid = found && near > 1e-4f;  // generate_voxel.py:397-400
     if (valid) {
         // the grid only gains bits: a stale read of a clear bit costs one redundant atomic, nothing else
@@ -105,22 +54,15 @@ __global__ void voxel_view_seen_kernel(NcwVoxelView cam, int level, float scale,
     if (depth) depth[k] = valid ? near * scale / dir_norm + 0.02f : 0.f;  // kaolin_renderer.py:127, 141
 }
 
-// The bit of each point's voxel; the voxel index is voxel_build_kernel's (ncw_voxel.hip), to the letter.
+// The bit of each point's voxel (voxel_of_point: the index voxel_build_kernel sets).
 __global__ void voxel_points_seen_kernel(const float* __restrict__ pts, int64_t n, int level, const uint32_t* __restrict__ seen,
                                          uint8_t* __restrict__ flags) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const int G = 1 << level;
     int c[3];
-    bool inside = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        const float u = (pts[i * 3 + a] + 1.0f) * (0.5f * (float)G);
-        if (!(u >= 0.f) || u >= (float)G) inside = false;  // outside the cube (or NaN)
-        c[a] = inside ? (int)u : 0;
-    }
     uint8_t f = 0;
-    if (inside) {
+    if (voxel_of_point(pts + i * 3, G, c)) {
         const int64_t v = ((int64_t)c[0] * G + c[1]) * G + c[2];
         f = (uint8_t)((seen[v >> 5] >> (v & 31)) & 1u);
     }

@@ -7,8 +7,8 @@ and the helpers of utils/eval_utils.py (`_compute` :87-100, `bbx_crop` :103-113,
 the nearest-neighbour queries with one scipy KDTree query per point; here:
   * nearest neighbours: exact 1-NN over a uniform grid (csrc/ncw_nn.hip, `nn_distances`) -- same distances, no
     approximation, ties to the smaller index;
-  * PLY input without trimesh (`read_ply_points`); the ONLY difference from trimesh's vertex array: trimesh merges duplicate
-    vertices when it loads a MESH, and `read_ply_points` removes exact-coordinate duplicates only (our own meshes are already
+  * PLY input without trimesh (`ply.read_points`); the ONLY difference from trimesh's vertex array: trimesh merges duplicate
+    vertices when it loads a MESH, and `ply.read_points` removes exact-coordinate duplicates only (our own meshes are already
     welded, so the step does nothing on them);
   * the SfM crop with sorted unique cell keys + searchsorted instead of the O(N M) Morton-code compare (`sfm_crop`);
   * all thresholds from one sort per distance vector (`metrics`).
@@ -28,7 +28,9 @@ import os
 import numpy as np
 import torch
 
+from . import colmap, ply
 from . import lib as L
+from .ply import read_points as read_ply_points  # noqa: F401  (a binding only: the name the earlier test suites call)
 
 F32_EPS = float(np.finfo(np.float32).eps)
 MAX_CELLS = 1 << 24  # cap of the dense cell table (two int32 per cell)
@@ -182,91 +184,6 @@ def nn_distances(ref, query, max_shell=MAX_SHELL, stats=None):
 # ---------------------------------------------------------------------------------------------------
 # PLY / COLMAP input
 # ---------------------------------------------------------------------------------------------------
-_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
-              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
-              "double": "f8", "float64": "f8"}
-
-
-def _ply_header(fh):
-    if fh.readline().strip() != b"ply":
-        raise ValueError("not a PLY file")
-    fmt, elements = None, []
-    while True:
-        line = fh.readline()
-        if not line:
-            raise ValueError("PLY header without end_header")
-        tok = line.decode("ascii", "replace").split()
-        if not tok or tok[0] in ("comment", "obj_info"):
-            continue
-        if tok[0] == "format":
-            fmt = tok[1]
-        elif tok[0] == "element":
-            elements.append({"name": tok[1], "count": int(tok[2]), "props": []})
-        elif tok[0] == "property":
-            if tok[1] == "list":
-                elements[-1]["props"].append((tok[4], "list", _PLY_TYPES[tok[2]], _PLY_TYPES[tok[3]]))
-            else:
-                elements[-1]["props"].append((tok[2], _PLY_TYPES[tok[1]], None, None))
-        elif tok[0] == "end_header":
-            return fmt, elements
-
-
-def read_ply_points(path, weld=None):
-    """float64 [V,3] vertex coordinates (x, y, z) of an ascii / binary_little_endian / binary_big_endian PLY with any vertex
-    property list; other elements (faces, ...) are skipped.  What trimesh.load(...).vertices gives (utils/eval_utils.py:65,71),
-    except for one thing: trimesh merges duplicate vertices when it loads a MESH -- here a file with faces (weld=None) or
-    weld=True drops exact-coordinate duplicates, first occurrence kept, order preserved.  mesh.write_ply's files are welded
-    already, so this changes nothing on them."""
-    with open(path, "rb") as fh:
-        fmt, elements = _ply_header(fh)
-        body = fh.read()
-    n_faces = sum(e["count"] for e in elements if e["name"] == "face")
-    verts = None
-    if fmt == "ascii":
-        lines = body.decode("ascii").splitlines()
-        row = 0
-        for e in elements:
-            if e["name"] == "vertex":
-                names = [p[0] for p in e["props"]]
-                if any(p[1] == "list" for p in e["props"]):
-                    raise ValueError("list property in the vertex element")
-                cols = [names.index(c) for c in ("x", "y", "z")]
-                data = np.array([lines[row + i].split() for i in range(e["count"])], dtype=np.float64).reshape(-1, len(names))
-                verts = data[:, cols]
-                break
-            row += e["count"]
-    elif fmt in ("binary_little_endian", "binary_big_endian"):
-        bo = "<" if fmt == "binary_little_endian" else ">"
-        off = 0
-        for e in elements:
-            if any(p[1] == "list" for p in e["props"]):
-                if e["name"] == "vertex":
-                    raise ValueError("list property in the vertex element")
-                for _ in range(e["count"]):  # variable-length rows: walk them
-                    for _, kind, ct, it in e["props"]:
-                        if kind == "list":
-                            cnt = int(np.frombuffer(body, bo + ct, 1, off)[0])
-                            off += np.dtype(ct).itemsize + cnt * np.dtype(it).itemsize
-                        else:
-                            off += np.dtype(kind).itemsize
-                continue
-            dt = np.dtype([(p[0], bo + p[1]) for p in e["props"]])
-            if e["name"] == "vertex":
-                rec = np.frombuffer(body, dt, e["count"], off)
-                verts = np.stack([rec[c].astype(np.float64) for c in ("x", "y", "z")], -1)
-                break
-            off += dt.itemsize * e["count"]
-    else:
-        raise ValueError("unknown PLY format %r" % fmt)
-    if verts is None:
-        verts = np.zeros((0, 3), dtype=np.float64)
-    verts = np.ascontiguousarray(verts, dtype=np.float64).reshape(-1, 3)
-    if (n_faces > 0 if weld is None else weld) and verts.shape[0]:
-        _, first = np.unique(verts, axis=0, return_index=True)
-        verts = verts[np.sort(first)]
-    return verts
-
-
 def apply_transform(points, T):
     """(T[:3] @ [p, 1]^T)^T in float64: the reference's homogeneous product (eval_utils.py:70-71, :167-168)."""
     T = np.asarray(T, dtype=np.float64)
@@ -279,11 +196,9 @@ def read_points3d_filtered(path, track_length, reproj_error, sfm_to_gt=None):
     """utils/eval_utils.py:157-173 `filtered_sfm`: COLMAP points with a track STRICTLY longer than `track_length` and a mean
     reprojection error STRICTLY below `reproj_error`, carried to GT coordinates by `sfm_to_gt` (4x4; None = identity).
     `path`: points3D.bin or the directory holding it.  float64 [K,3] ([0,3] when none passes; the reference raises there)."""
-    from . import voxel
-
     if os.path.isdir(path):
         path = os.path.join(path, "points3D.bin")
-    xyz, err, track = voxel.read_points3d(path)
+    _, xyz, err, track = colmap.read_points3d(path)
     keep = (track > track_length) & (err < reproj_error)
     pts = xyz[keep]
     return pts if sfm_to_gt is None else apply_transform(pts, sfm_to_gt)
@@ -565,25 +480,21 @@ def error_colours(dists, threshold):
 
 
 def _write_error_cloud(path, pts, dists, threshold):
-    from . import reproj
-
     xyz = pts.detach().cpu().numpy() if torch.is_tensor(pts) else pts
-    reproj.write_ply_points(path, xyz, error_colours(dists, threshold).cpu().numpy())
+    ply.write(path, xyz, rgb=error_colours(dists, threshold).cpu().numpy())
 
 
 # ---------------------------------------------------------------------------------------------------
 # the evaluation (utils/eval_mesh.py:48-123, both branches)
 # ---------------------------------------------------------------------------------------------------
 def _write_points(path, pts):
-    from . import mesh
-
-    v = torch.from_numpy(np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 3))
-    mesh.write_ply(path, v, torch.zeros(0, 3, dtype=torch.int64))
+    """The clouds of the vertex scoring, as trimesh exports them: float coordinates and an empty face element."""
+    ply.write(path, pts, faces=np.zeros((0, 3), dtype=np.int64), coord="f4")
 
 
 def eval_mesh(file_pred, file_trgt, scene_config, is_mesh, threshold=.1, bbx_name="eval_bbx", save_name="eval", sfm=None,
               device=None, verbose=True, surface=None, surface_seed=0, surface_mode="stratified", error_clouds=None):
-    """utils/eval_mesh.py:48-123 with use_o3d=False: load both PLYs (read_ply_points; `is_mesh` is accepted and, as in the
+    """utils/eval_mesh.py:48-123 with use_o3d=False: load both PLYs (ply.read_points; `is_mesh` is accepted and, as in the
     reference's trimesh branch, not used), carry the prediction to GT coordinates by scene_config['sfm2gt'], crop both to
     scene_config[bbx_name], optionally crop both to the voxels of the filtered SfM points, nearest neighbours in both
     directions on the GPU, metrics per threshold.  `sfm`: dict(path, track_length, reproj_error, voxel_size), or the
@@ -593,7 +504,7 @@ def eval_mesh(file_pred, file_trgt, scene_config, is_mesh, threshold=.1, bbx_nam
     last threshold's metrics dict.
 
     `surface` = k (a number; the reference's value is 10) scores the prediction by its SURFACE, as the reference's open3d
-    branch does with is_mesh (utils/eval_utils.py:30-43): file_pred must have faces (reproj.read_ply_mesh, vertices as
+    branch does with is_mesh (utils/eval_utils.py:30-43): file_pred must have faces (ply.read_mesh, vertices as
     stored); its vertices are carried to GT coordinates, the triangles with all three corners inside the closed box are kept
     (open3d's documented crop rule; unpinned), int(|cropped GT|) * k points are drawn uniformly by area on the GPU
     (`sample_surface` with surface_seed / surface_mode) and written to down_pred_in_gt.ply as doubles (open3d's
@@ -610,22 +521,20 @@ def eval_mesh(file_pred, file_trgt, scene_config, is_mesh, threshold=.1, bbx_nam
     log("results will save in %s" % save_dir)
     sfm_to_gt = np.array(scene_config["sfm2gt"], dtype=np.float64)
 
-    verts_trgt = bbx_crop(read_ply_points(file_trgt), scene_config[bbx_name])
+    verts_trgt = bbx_crop(ply.read_points(file_trgt), scene_config[bbx_name])
     _write_points(os.path.join(save_dir, "down_gt.ply"), verts_trgt)
     if surface is None:
-        verts_pred = bbx_crop(apply_transform(read_ply_points(file_pred), sfm_to_gt), scene_config[bbx_name])
+        verts_pred = bbx_crop(apply_transform(ply.read_points(file_pred), sfm_to_gt), scene_config[bbx_name])
         _write_points(os.path.join(save_dir, "down_pred_in_gt.ply"), verts_pred)
     else:
-        from . import reproj  # reproj imports this module: bound here, not at import time
-
-        m_verts, m_faces, _ = reproj.read_ply_mesh(file_pred)
+        m_verts, m_faces, _ = ply.read_mesh(file_pred)
         if m_faces.shape[0] == 0:
             raise ValueError("%s has no faces: surface sampling needs a triangle mesh (surface=None scores points)" % file_pred)
         n_samples = int(int(verts_trgt.shape[0]) * surface)
         verts_pred = sample_surface(apply_transform(m_verts, sfm_to_gt), m_faces, n_samples, seed=surface_seed,
                                     mode=surface_mode, box=scene_config[bbx_name], device=dev)
         log("surface samples: %d" % verts_pred.shape[0])
-        reproj.write_ply_points(os.path.join(save_dir, "down_pred_in_gt.ply"), verts_pred.cpu().numpy())
+        ply.write(os.path.join(save_dir, "down_pred_in_gt.ply"), verts_pred.cpu().numpy())
 
     if sfm is None and "sfm_path" in scene_config:
         sfm = {"path": scene_config["sfm_path"], "track_length": scene_config["eval_tl"],
@@ -636,7 +545,7 @@ def eval_mesh(file_pred, file_trgt, scene_config, is_mesh, threshold=.1, bbx_nam
         log("filtered points: %d" % sfm_pts.shape[0])
         verts_pred = sfm_crop(verts_pred, sfm_pts, sfm["voxel_size"], scene_config[bbx_name])
         if torch.is_tensor(verts_pred):
-            reproj.write_ply_points(os.path.join(save_dir, "pred_filtered.ply"), verts_pred.cpu().numpy())
+            ply.write(os.path.join(save_dir, "pred_filtered.ply"), verts_pred.cpu().numpy())
         else:
             _write_points(os.path.join(save_dir, "pred_filtered.ply"), verts_pred)
         verts_trgt = sfm_crop(verts_trgt, sfm_pts, sfm["voxel_size"], scene_config[bbx_name])

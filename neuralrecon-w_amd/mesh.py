@@ -16,6 +16,7 @@ import torch
 
 from . import grid as _grid
 from . import lib as L
+from . import ply
 
 
 _TABLES = {}
@@ -170,23 +171,7 @@ def extract_mesh(renderer, dim, scene_radius, scene_origin, origin=None, radius=
 
 
 def write_ply(path, vertices, faces, colors=None):
-    """Binary little-endian PLY (what trimesh's export writes for tools/extract_mesh.py:160-168)."""
-    v = vertices.detach().cpu().numpy().astype("<f4")
-    f = faces.detach().cpu().numpy().astype("<i4")
-    hdr = ["ply", "format binary_little_endian 1.0", "element vertex %d" % v.shape[0], "property float x",
-           "property float y", "property float z"]
-    if colors is not None:
-        hdr += ["property uchar red", "property uchar green", "property uchar blue"]
-    hdr += ["element face %d" % f.shape[0], "property list uchar int vertex_indices", "end_header"]
-    with open(path, "wb") as fh:
-        fh.write(("\n".join(hdr) + "\n").encode("ascii"))
-        if colors is None:
-            fh.write(v.tobytes())
-        else:
-            c = colors.detach().cpu().numpy().astype("u1")
-            rec = np.empty(v.shape[0], dtype=[("p", "<f4", 3), ("c", "u1", 3)])
-            rec["p"], rec["c"] = v, c
-            fh.write(rec.tobytes())
-        rec = np.empty(f.shape[0], dtype=[("n", "u1"), ("i", "<i4", 3)])
-        rec["n"], rec["i"] = 3, f
-        fh.write(rec.tobytes())
+    """Binary little-endian PLY of device tensors (what trimesh's export writes for tools/extract_mesh.py:160-168): float
+    coordinates, uchar colours, always a face element."""
+    ply.write(path, vertices.detach().cpu().numpy(), faces.detach().cpu().numpy(),
+              None if colors is None else colors.detach().cpu().numpy(), coord="f4")

@@ -8,33 +8,30 @@ every valid pixel and runs one open3d KD-tree query per pixel in a Python loop; 
   * depth: the triangle rasterizer of csrc/ncw_raster.hip (`render_depth`), pyrender's conventions (see INTEGRATION.md);
   * back-projection and marking: ncw_raster_backproject / ncw_raster_mark, nearest neighbours by evalmesh.NNGrid (exact,
     ties to the smaller index);
-  * COLMAP cameras.bin / images.bin and the tsv split read here (no pandas, no open3d, no trimesh); PINHOLE cameras only;
+  * COLMAP cameras.bin / images.bin, the tsv split and PLY files read by colmap.py / ply.py (no pandas, no open3d, no trimesh);
+    PINHOLE cameras only;
   * one process, one GPU: the views are independent and run one after another;
   * a source WITHOUT faces (a point cloud: utils/reproj_filter.py:110-115, utils/kaolin_renderer.py) is voxelised over the
     evaluation box (`VoxelCloud`) and every view is traced to the first occupied voxel by csrc/ncw_voxview.hip.
 """
-import csv
 import ctypes as C
-import glob
 import os
-import struct
 
 import numpy as np
 import torch
 import yaml
 
-from . import evalmesh
+from . import colmap, evalmesh, ply
 from . import lib as L
+# The names the test suites of the earlier commits call (tests/test_reproj_host.py, tests/test_gpu_reproj*.py, tests/test_gpu_surf.py):
+# bindings only -- the functions live in colmap.py / ply.py, and the package's own code calls them there.
+from .colmap import qvec2rotmat, read_cameras as read_cameras_binary, read_images as read_images_binary  # noqa: F401
+from .ply import read_mesh as read_ply_mesh  # noqa: F401
 
 ZNEAR, ZFAR = 0.05, 100.0  # pyrender.IntrinsicsCamera's defaults (in the units of the rendered frame)
 SMALL_MAX = 32  # sub-triangles whose pixel box holds more samples go to the workgroup-per-triangle kernel
 CULL = {"back": 1, "none": 0}
 
-# COLMAP camera models: id -> (name, number of parameters)
-CAMERA_MODELS = {0: ("SIMPLE_PINHOLE", 3), 1: ("PINHOLE", 4), 2: ("SIMPLE_RADIAL", 4), 3: ("RADIAL", 5), 4: ("OPENCV", 8),
-                 5: ("OPENCV_FISHEYE", 8), 6: ("FULL_OPENCV", 12), 7: ("FOV", 5), 8: ("SIMPLE_RADIAL_FISHEYE", 4),
-                 9: ("RADIAL_FISHEYE", 5), 10: ("THIN_PRISM_FISHEYE", 12)}
-PINHOLE = 1
 # what pandas.read_csv reads as a missing value (its default na_values): such an `id` is null
 _NA = {"", "#N/A", "#N/A N/A", "#NA", "-1.#IND", "-1.#QNAN", "-NaN", "-nan", "1.#IND", "1.#QNAN", "<NA>", "N/A", "NA", "NULL",
        "NaN", "None", "n/a", "nan", "null"}
@@ -43,72 +40,21 @@ _NA = {"", "#N/A", "#N/A N/A", "#NA", "-1.#IND", "-1.#QNAN", "-NaN", "-nan", "1.
 # ---------------------------------------------------------------------------------------------------
 # COLMAP model and the train split
 # ---------------------------------------------------------------------------------------------------
-def read_cameras_binary(path):
-    """COLMAP cameras.bin: {camera_id: dict(id, model, width, height, params float64)}.  Layout (little-endian): uint64
-    count, then per camera int32 id, int32 model id, uint64 width, uint64 height, float64 params[n(model)].  Only PINHOLE
-    cameras (fx, fy, cx, cy) are accepted: any other model is refused with a ValueError (the reference would read the
-    first four parameters of any model as fx, fy, cx, cy)."""
-    cams = {}
-    with open(path, "rb") as fh:
-        (n,) = struct.unpack("<Q", fh.read(8))
-        for _ in range(n):
-            cid, model, width, height = struct.unpack("<iiQQ", fh.read(24))
-            if model != PINHOLE:
-                name = CAMERA_MODELS.get(model, ("unknown model id %d" % model,))[0]
-                raise ValueError("%s: camera %d is %s; only PINHOLE cameras (undistorted images) are supported" % (path, cid, name))
-            params = np.frombuffer(fh.read(8 * 4), dtype="<f8").astype(np.float64)
-            cams[cid] = {"id": cid, "model": model, "width": int(width), "height": int(height), "params": params}
-    return cams
-
-
-def read_images_binary(path):
-    """COLMAP images.bin: {image_id: dict(id, qvec, tvec, camera_id, name)} (the 2-D points are skipped).  Layout: uint64
-    count, then per image int32 id, float64 qvec[4] (w, x, y, z), float64 tvec[3], int32 camera id, the name as
-    NUL-terminated bytes, uint64 n2d, n2d x (float64 x, float64 y, int64 point3D id)."""
-    imgs = {}
-    with open(path, "rb") as fh:
-        (n,) = struct.unpack("<Q", fh.read(8))
-        for _ in range(n):
-            rec = struct.unpack("<i7di", fh.read(64))
-            name = bytearray()
-            while True:
-                ch = fh.read(1)
-                if ch in (b"\x00", b""):
-                    break
-                name += ch
-            (n2d,) = struct.unpack("<Q", fh.read(8))
-            fh.seek(24 * n2d, os.SEEK_CUR)
-            imgs[rec[0]] = {"id": rec[0], "qvec": np.array(rec[1:5]), "tvec": np.array(rec[5:8]), "camera_id": rec[8],
-                            "name": name.decode("utf-8")}
-    return imgs
-
-
-def qvec2rotmat(q):
-    """Rotation of the unit quaternion (w, x, y, z) (COLMAP's convention: world -> camera)."""
-    w, x, y, z = [float(v) for v in q]
-    return np.array([[1 - 2 * y * y - 2 * z * z, 2 * x * y - 2 * w * z, 2 * z * x + 2 * w * y],
-                     [2 * x * y + 2 * w * z, 1 - 2 * x * x - 2 * z * z, 2 * y * z - 2 * w * x],
-                     [2 * z * x - 2 * w * y, 2 * y * z + 2 * w * x, 1 - 2 * x * x - 2 * y * y]])
-
-
 def read_train_split(data_path, images):
     """utils/reproj_filter.py:70-83 `get_train_ids`: the rows of the first <data_path>/*.tsv (sorted by name) with a non-null
     `id` and split == 'train', in file order, as COLMAP image ids (through the image names).  A filename of a row with an
     id that is not in images.bin is an error, as in the reference."""
-    tsvs = sorted(glob.glob(os.path.join(data_path, "*.tsv")))
-    if not tsvs:
-        raise FileNotFoundError("no *.tsv split file in %s" % data_path)
+    tsv, rows = colmap.split_rows(data_path)
     by_name = {im["name"]: iid for iid, im in images.items()}
     ids = []
-    with open(tsvs[0], newline="") as fh:
-        for row in csv.DictReader(fh, delimiter="\t"):
-            if (row.get("id") or "").strip() in _NA:
-                continue
-            name = row["filename"]
-            if name not in by_name:
-                raise KeyError("%s: image %r is not in images.bin" % (tsvs[0], name))
-            if row.get("split") == "train":
-                ids.append(by_name[name])
+    for row in rows:
+        if (row.get("id") or "").strip() in _NA:
+            continue
+        name = row["filename"]
+        if name not in by_name:
+            raise KeyError("%s: image %r is not in images.bin" % (tsv, name))
+        if row.get("split") == "train":
+            ids.append(by_name[name])
     return ids
 
 
@@ -117,8 +63,8 @@ def load_views(data_path, sfm2gt=None):
     values, as tools/reproj_error.py:84-88 builds it), wh (width, height), E_gt = E inv(sfm2gt) (utils/reproj_filter.py:175),
     pose = inv(E_gt))."""
     sp = os.path.join(data_path, "dense", "sparse")
-    images = read_images_binary(os.path.join(sp, "images.bin"))
-    cams = read_cameras_binary(os.path.join(sp, "cameras.bin"))
+    images = colmap.read_images(os.path.join(sp, "images.bin"))
+    cams = colmap.read_cameras(os.path.join(sp, "cameras.bin"))
     S = np.eye(4) if sfm2gt is None else np.asarray(sfm2gt, dtype=np.float64)
     S_inv = np.linalg.inv(S)
     views = []
@@ -126,7 +72,7 @@ def load_views(data_path, sfm2gt=None):
         im = images[iid]
         cam = cams[im["camera_id"]]
         E = np.eye(4)
-        E[:3, :3] = qvec2rotmat(im["qvec"])
+        E[:3, :3] = colmap.qvec2rotmat(im["qvec"])
         E[:3, 3] = im["tvec"]
         p = cam["params"]
         K = np.array([[p[0], 0, p[2]], [0, p[1], p[3]], [0, 0, 1]], dtype=np.float32)
@@ -141,95 +87,10 @@ def read_sfm2gt(data_path):
         return np.array(yaml.safe_load(fh)["sfm2gt"], dtype=np.float64)
 
 
-# ---------------------------------------------------------------------------------------------------
-# PLY
-# ---------------------------------------------------------------------------------------------------
-def read_ply_mesh(path):
-    """(vertices float64 [V,3], faces int64 [F,3], colours uint8 [V,3] or None) of an ascii / binary PLY, vertices as stored
-    (no welding: trimesh.load(process=False) and open3d.io.read_point_cloud read them so).  Colours: the vertex properties
-    red / green / blue (uchar; other integer types are cast).  Faces: the `vertex_indices` / `vertex_index` list of the face
-    element; polygons with more than three corners are fanned (0, i, i + 1) as trimesh does."""
-    with open(path, "rb") as fh:
-        fmt, elements = evalmesh._ply_header(fh)
-        body = fh.read()
-    verts = np.zeros((0, 3))
-    cols, faces = None, np.zeros((0, 3), dtype=np.int64)
-
-    def vertex_arrays(get):
-        v = np.stack([get(c).astype(np.float64) for c in ("x", "y", "z")], -1).reshape(-1, 3)
-        names = get(None)
-        c = None
-        if all(k in names for k in ("red", "green", "blue")):
-            c = np.stack([get(k) for k in ("red", "green", "blue")], -1).astype(np.uint8).reshape(-1, 3)
-        return v, c
-
-    def fan(polys):
-        tri = [np.stack([p[0].repeat(len(p) - 2), p[1:-1], p[2:]], -1) for p in polys if len(p) >= 3]
-        return np.concatenate(tri).astype(np.int64) if tri else np.zeros((0, 3), dtype=np.int64)
-
-    if fmt == "ascii":
-        lines = body.decode("ascii").splitlines()
-        row = 0
-        for e in elements:
-            rows = [lines[row + i].split() for i in range(e["count"])]
-            row += e["count"]
-            if e["name"] == "vertex":
-                names = [p[0] for p in e["props"]]
-                data = np.array(rows, dtype=np.float64).reshape(-1, len(names))
-                verts, cols = vertex_arrays(lambda k: names if k is None else data[:, names.index(k)])
-            elif e["name"] == "face":
-                polys = []
-                for r in rows:  # the index list is the first property of the face element in every file we read
-                    cnt = int(r[0])
-                    polys.append(np.array(r[1:1 + cnt], dtype=np.int64))
-                faces = fan(polys)
-    elif fmt in ("binary_little_endian", "binary_big_endian"):
-        bo = "<" if fmt == "binary_little_endian" else ">"
-        off = 0
-        for e in elements:
-            if any(p[1] == "list" for p in e["props"]):
-                polys = []
-                for _ in range(e["count"]):
-                    for name, kind, ct, it in e["props"]:
-                        if kind == "list":
-                            cnt = int(np.frombuffer(body, bo + ct, 1, off)[0])
-                            off += np.dtype(ct).itemsize
-                            vals = np.frombuffer(body, bo + it, cnt, off)
-                            off += cnt * np.dtype(it).itemsize
-                            if e["name"] == "face" and name in ("vertex_indices", "vertex_index"):
-                                polys.append(vals.astype(np.int64))
-                        else:
-                            off += np.dtype(kind).itemsize
-                if e["name"] == "face":
-                    faces = fan(polys)
-                continue
-            dt = np.dtype([(p[0], bo + p[1]) for p in e["props"]])
-            rec = np.frombuffer(body, dt, e["count"], off)
-            off += dt.itemsize * e["count"]
-            if e["name"] == "vertex":
-                names = [p[0] for p in e["props"]]
-                verts, cols = vertex_arrays(lambda k: names if k is None else rec[k])
-    else:
-        raise ValueError("unknown PLY format %r" % fmt)
-    return np.ascontiguousarray(verts, dtype=np.float64), np.ascontiguousarray(faces, dtype=np.int64), cols
-
-
 def write_ply_points(path, xyz, rgb=None):
-    """Binary little-endian PLY point cloud: double x / y / z, uchar red / green / blue (what open3d's write_point_cloud
-    writes for utils/reproj_filter.py:293-300)."""
-    xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
-    hdr = ["ply", "format binary_little_endian 1.0", "element vertex %d" % xyz.shape[0], "property double x",
-           "property double y", "property double z"]
-    if rgb is not None:
-        hdr += ["property uchar red", "property uchar green", "property uchar blue"]
-    hdr.append("end_header")
-    rec = np.empty(xyz.shape[0], dtype=[("p", "<f8", 3)] + ([("c", "u1", 3)] if rgb is not None else []))
-    rec["p"] = xyz
-    if rgb is not None:
-        rec["c"] = np.asarray(rgb).reshape(-1, 3)
-    with open(path, "wb") as fh:
-        fh.write(("\n".join(hdr) + "\n").encode("ascii"))
-        fh.write(rec.tobytes())
+    """ply.write's point-cloud form (double coordinates, optional uchar colours, no face element) under the name the earlier
+    test suites call; the package itself calls ply.write."""
+    ply.write(path, xyz, rgb=rgb)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -536,18 +397,18 @@ def reproj_filter(src_file, target_file, data_path, output_path, gt=False, voxel
     views = load_views(data_path, S)
     log("views to process: %d" % len(views))
 
-    t_xyz, _, t_rgb = read_ply_mesh(target_file)
+    t_xyz, _, t_rgb = ply.read_mesh(target_file)
     if not gt:
         t_xyz = evalmesh.apply_transform(t_xyz, S)
     if t_rgb is None:
         log("No color found in target point cloud")
 
-    s_verts, s_faces, _ = read_ply_mesh(src_file)
+    s_verts, s_faces, _ = ply.read_mesh(src_file)
     if s_faces.shape[0] == 0:
         log("reproject point cloud")
         xyz, rgb = _filter_cloud(s_verts if gt else evalmesh.apply_transform(s_verts, S), t_xyz, t_rgb, views, scene_config,
                                  output_path, voxel_size, visualize, dev)
-        write_ply_points(os.path.join(output_path, "reprojected.ply"), xyz, rgb)
+        ply.write(os.path.join(output_path, "reprojected.ply"), xyz, rgb=rgb)
         log("kept %d of %d vertices" % (xyz.shape[0], t_xyz.shape[0]))
         return xyz, rgb
     target = Target(t_xyz, t_rgb, 2 * np.sqrt(2) * voxel_size, dev)
@@ -571,10 +432,10 @@ def reproj_filter(src_file, target_file, data_path, output_path, gt=False, voxel
             for sub in ("depth", "reprojects"):
                 os.makedirs(os.path.join(output_path, "render", sub), exist_ok=True)
             np.save(os.path.join(output_path, "render", "depth", stem + ".npy"), depth.cpu().numpy())
-            write_ply_points(os.path.join(output_path, "render", "reprojects", stem + ".ply"),
-                             pts.double().cpu().numpy() + target.centre)
+            ply.write(os.path.join(output_path, "render", "reprojects", stem + ".ply"),
+                      pts.double().cpu().numpy() + target.centre)
     xyz, rgb = target.rows()
-    write_ply_points(os.path.join(output_path, "reprojected.ply"), xyz, rgb)
+    ply.write(os.path.join(output_path, "reprojected.ply"), xyz, rgb=rgb)
     log("kept %d of %d vertices" % (xyz.shape[0], target.m))
     return xyz, rgb
 
@@ -596,8 +457,8 @@ def _filter_cloud(s_xyz, t_xyz, t_rgb, views, scene_config, output_path, voxel_s
                 os.makedirs(os.path.join(output_path, "render", sub), exist_ok=True)
             np.save(os.path.join(output_path, "render", "depth", stem + ".npy"), depth.view(h, w).cpu().numpy())
             pts, _ = backproject(depth.view(h, w), backproject_matrix(v["K"], v["pose"], cloud.origin))
-            write_ply_points(os.path.join(output_path, "render", "reprojects", stem + ".ply"),
-                             pts.double().cpu().numpy() + cloud.origin)
+            ply.write(os.path.join(output_path, "render", "reprojects", stem + ".ply"),
+                      pts.double().cpu().numpy() + cloud.origin)
     t_xyz = np.ascontiguousarray(t_xyz, dtype=np.float64).reshape(-1, 3)
     rgb = np.zeros(t_xyz.shape, dtype=np.uint8) if t_rgb is None else np.asarray(t_rgb, dtype=np.uint8).reshape(-1, 3)
     return unique_rows(t_xyz, rgb, cloud.select(t_xyz), dev)

@@ -10,7 +10,6 @@ The rays of a pixel chunk are generated on the device (`ncw_view_rays`), rendere
 `ncw_image_*` / `ncw_depth_colormap` launches (csrc/ncw_view.hip).  Nothing is copied to the host per chunk.
 """
 import ctypes as C
-import glob
 import os
 import struct
 import zlib
@@ -18,6 +17,7 @@ import zlib
 import numpy as np
 import torch
 
+from . import colmap
 from . import lib as L
 
 DEFAULT_CHUNK = 4096  # rays per render launch (scripts/bench_view.py measures 1024 / 4096 / 16384: profiles/view/README.md)
@@ -260,44 +260,36 @@ def reference_sfm_path(root_dir):
     return "../neuralsfm" if name in ("brandenburg_gate", "palacio_de_bellas_artes") else "sparse"
 
 
-def read_scene(root_dir, sfm_path=None):
+def read_scene(root_dir, sfm_path=None, with_points=False):
     """What the reference's dataset reads ONCE per scene (datasets/phototourism.py:316-350, 360, 453-462): the COLMAP model under
     <root_dir>/dense/<sfm_path> (None = `reference_sfm_path`) and the first *.tsv.  Returns a dict: `sp` (the model directory),
-    `images` / `cams` (reproj.read_images_binary / read_cameras_binary), `tsv`, `by_name` {file name: image id}, `ids` (the tsv's
-    images that are registered in images.bin, file order) and `ids_train` (those whose split is not 'test')."""
-    from . import reproj
-
+    `images` / `cams` (colmap.read_images / read_cameras), `tsv`, `by_name` {file name: image id}, `ids` (the tsv's
+    images that are registered in images.bin, file order) and `ids_train` (those whose split is not 'test').  with_points: the
+    images carry their 2-D points (colmap.read_images), which the ray cache needs."""
     if sfm_path is None:
         sfm_path = reference_sfm_path(root_dir)
     sp = os.path.normpath(os.path.join(root_dir, "dense", sfm_path))
     if not os.path.isfile(os.path.join(sp, "images.bin")):
         raise FileNotFoundError("no COLMAP model in %s (sfm_path %r): pass sfm_path / --sfm_path for the model the ray cache "
                                 "was built from" % (sp, sfm_path))
-    images = reproj.read_images_binary(os.path.join(sp, "images.bin"))
-    cams = reproj.read_cameras_binary(os.path.join(sp, "cameras.bin"))
-    tsvs = glob.glob(os.path.join(root_dir, "*.tsv"))
-    if not tsvs:
-        raise FileNotFoundError("no *.tsv split file in %s" % root_dir)
-    import csv
-
+    images = colmap.read_images(os.path.join(sp, "images.bin"), with_points)
+    cams = colmap.read_cameras(os.path.join(sp, "cameras.bin"))
+    tsv, rows = colmap.split_rows(root_dir)
     by_name = {im["name"]: iid for iid, im in images.items()}
     ids, ids_train = [], []
-    with open(sorted(tsvs)[0], newline="") as fh:
-        for row in csv.DictReader(fh, delimiter="\t"):
-            if row["filename"] not in by_name:  # "image ... not found in sfm result" (:345-347)
-                continue
-            ids.append(by_name[row["filename"]])
-            if row.get("split") != "test":
-                ids_train.append(ids[-1])
-    return {"sp": sp, "sfm_path": sfm_path, "images": images, "cams": cams, "tsv": sorted(tsvs)[0], "by_name": by_name, "ids": ids,
+    for row in rows:
+        if row["filename"] not in by_name:  # "image ... not found in sfm result" (:345-347)
+            continue
+        ids.append(by_name[row["filename"]])
+        if row.get("split") != "test":
+            ids_train.append(ids[-1])
+    return {"sp": sp, "sfm_path": sfm_path, "images": images, "cams": cams, "tsv": tsv, "by_name": by_name, "ids": ids,
             "ids_train": ids_train}
 
 
 def image_pose(scene, image_id, downscale):
     """K [3,3] f32 rescaled by (size // downscale) / size with the reference's size int(2 cx) x int(2 cy) (phototourism.py:367-375),
     w2c [4,4] f64, c2w [3,4] f64 = inv(w2c)[:3] with columns 1, 2 negated (:406-408), and the rescaled size (w, h)."""
-    from . import reproj
-
     im = scene["images"][image_id]
     p = scene["cams"][im["camera_id"]]["params"]
     img_w, img_h = int(p[2] * 2), int(p[3] * 2)
@@ -307,7 +299,7 @@ def image_pose(scene, image_id, downscale):
     K[0, 2], K[1, 2] = p[2] * w_ / img_w, p[3] * h_ / img_h
     K[2, 2] = 1
     w2c = np.eye(4)
-    w2c[:3, :3], w2c[:3, 3] = reproj.qvec2rotmat(im["qvec"]), im["tvec"]
+    w2c[:3, :3], w2c[:3, 3] = colmap.qvec2rotmat(im["qvec"]), im["tvec"]
     c2w = np.linalg.inv(w2c)[:3].copy()
     c2w[:, 1:3] *= -1
     return K, w2c, c2w, w_, h_
@@ -316,15 +308,13 @@ def image_pose(scene, image_id, downscale):
 def image_near_far(scene, w2c, scene_origin=None, scene_radius=None):
     """phototourism.py:426-444: the 0.1 / 99.9 percentiles of the depths of the SfM points in front of the camera, or
     origin_z -+ 1.5 radius when scene_origin (SfM frame) and scene_radius are given.  points3D.bin is read once per scene."""
-    from . import voxel
-
     if scene_origin is not None:
         if scene_radius is None:
             raise ValueError("scene_view: scene_origin needs scene_radius")
         oz = (np.concatenate([np.asarray(scene_origin, dtype=np.float64), np.ones(1)])[None] @ w2c.T)[0, 2]
         return oz - float(scene_radius) * 1.5, oz + float(scene_radius) * 1.5
     if "xyz_h" not in scene:
-        xyz, _, _ = voxel.read_points3d(os.path.join(scene["sp"], "points3D.bin"))
+        _, xyz, _, _ = colmap.read_points3d(os.path.join(scene["sp"], "points3D.bin"))
         scene["xyz_h"] = np.concatenate([xyz, np.ones((len(xyz), 1))], -1)
     z = (scene["xyz_h"] @ w2c.T)[:, 2]
     z = z[z > 0]

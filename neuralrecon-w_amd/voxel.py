@@ -10,6 +10,7 @@ import math
 
 import torch
 
+from . import colmap
 from . import lib as L
 from . import spc
 
@@ -91,35 +92,10 @@ def occupancy_from_dense(dense_bool, scene_origin, scale, voxel_size=None):
     return occupancy_from_points(centres * float(scale) + origin, scene_origin, scale, level, voxel_size)
 
 
-def read_points3d(path):
-    """COLMAP `points3D.bin` (utils/colmap_utils.py:264-291: u64 count, then per point `<QdddBBBd` + u64 track
-    length + that many `<ii` track elements) -> (xyz float64 [N,3], reprojection error float64 [N], track length
-    int64 [N]), file order."""
-    import struct
-
-    import numpy as np
-
-    with open(path, "rb") as f:
-        buf = f.read()
-    (n,) = struct.unpack_from("<Q", buf, 0)
-    off = 8
-    xyz = np.empty((n, 3), dtype=np.float64)
-    err = np.empty(n, dtype=np.float64)
-    track = np.empty(n, dtype=np.int64)
-    for i in range(n):
-        xyz[i] = struct.unpack_from("<ddd", buf, off + 8)
-        (err[i],) = struct.unpack_from("<d", buf, off + 35)
-        (track[i],) = struct.unpack_from("<Q", buf, off + 43)
-        off += 51 + 8 * int(track[i])
-    if off != len(buf):
-        raise ValueError("%s: %d trailing bytes after %d points (not a COLMAP points3D.bin?)" % (path, len(buf) - off, n))
-    return xyz, err, track
-
-
 def read_points3d_xyz(path, min_track_length):
-    """float64 [N,3] xyz of the COLMAP points (read_points3d) whose track is LONGER than `min_track_length`
+    """float64 [N,3] xyz of the COLMAP points (colmap.read_points3d) whose track is LONGER than `min_track_length`
     (generate_voxel.py:55-58: `p.point2D_idxs.shape[0] > min_track_length`), file order."""
-    xyz, _, track = read_points3d(path)
+    _, xyz, _, track = colmap.read_points3d(path)
     return xyz[track > min_track_length].reshape(-1, 3)
 
 

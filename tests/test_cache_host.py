@@ -32,11 +32,11 @@ def test_scene_lists_are_the_datasets(g):
 
 
 def test_readers_match_the_reference_tables(g):
-    from neuralrecon_w_amd import cachebuild
+    from neuralrecon_w_amd import cachebuild, colmap
 
     xyz_t, err_t = cachebuild.read_points3d_table(os.path.join(SPARSE, "points3D.bin"))
     assert xyz_t.dtype == np.float32 and np.array_equal(xyz_t, g["xyz_table"]) and np.array_equal(err_t, g["err_table"])
-    pts = cachebuild.read_image_points(os.path.join(SPARSE, "images.bin"))
+    pts = {i: (im["xys"], im["point3d_ids"]) for i, im in colmap.read_images(os.path.join(SPARSE, "images.bin"), True).items()}
     assert sorted(pts) == sorted(g["ids"].tolist())
     for iid in g["ids"].tolist():
         t = "im%d_" % iid

@@ -121,12 +121,12 @@ def test_scene_view_matches_the_reference_dataset(gold, tag, kw):
     assert float((rays[:, :6] - ref[:, :6]).abs().max()) < 2e-6
     assert torch.equal(rays[:, 6:].float(), ref[:, 6:].float())
     # ... and the independent restatement of the dataset's steps from the raw COLMAP records
-    from neuralrecon_w_amd import reproj, voxel
+    from neuralrecon_w_amd import colmap
 
     sp = os.path.join(SCENE, "dense", "sparse")
-    im = reproj.read_images_binary(os.path.join(sp, "images.bin"))[image_id]
-    camrec = reproj.read_cameras_binary(os.path.join(sp, "cameras.bin"))[im["camera_id"]]
-    xyz, _, _ = voxel.read_points3d(os.path.join(sp, "points3D.bin"))
+    im = colmap.read_images(os.path.join(sp, "images.bin"))[image_id]
+    camrec = colmap.read_cameras(os.path.join(sp, "cameras.bin"))[im["camera_id"]]
+    _, xyz, _, _ = colmap.read_points3d(os.path.join(sp, "points3D.bin"))
     K, c2w, near, far = VR.scene_item(camrec["params"], im["qvec"], im["tvec"], xyz, int(gold[tag + "_downscale"]),
                                       kw.get("scene_origin"), kw.get("scene_radius"))
     assert np.array_equal(K, cam.K) and np.abs(c2w - cam.c2w).max() <= 1e-6
