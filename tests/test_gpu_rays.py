@@ -3,6 +3,7 @@ golden vectors of the real reference."""
 import pytest
 import torch
 
+from tests._ray_cases import comp_inputs as _comp_inputs
 from tests._util import load_golden, rel_err, synth_rays
 
 pytestmark = pytest.mark.gpu
@@ -73,27 +74,6 @@ def test_sample_coarse_vs_oracle(perturb):
     assert rel_err(z.cpu(), z_ref) < 1e-6
     assert rel_err(zo.cpu(), zo_ref) < 1e-6
     assert rel_err(sd.cpu(), sd_ref) < 1e-6
-
-
-def _comp_inputs(R, S, O_, seed, with_bg=True):
-    g = torch.Generator().manual_seed(seed)
-    rays, _, _, _ = synth_rays(R, seed, 10)
-    o, d = rays[:, 0:3], rays[:, 3:6]
-    z = torch.sort(1.0 + 2.2 * torch.rand(R, S, generator=g), -1)[0]
-    sample_dist = torch.full((R, 1), 2.0 / S)
-    mid = z + torch.cat([z[:, 1:] - z[:, :-1], sample_dist], -1) * 0.5
-    pts = o[:, None] + d[:, None] * mid[..., None]
-    sdf = pts.norm(dim=-1) - 0.5 + 0.01 * torch.randn(R, S, generator=g)
-    grad = pts / pts.norm(dim=-1, keepdim=True) * (1 + 0.1 * torch.randn(R, S, 1, generator=g)) \
-        + 0.05 * torch.randn(R, S, 3, generator=g)
-    rgb = torch.rand(R, S, 3, generator=g)
-    z_out = 3.3 + torch.sort(torch.rand(R, O_, generator=g), -1)[0] * 5
-    z_feed = torch.sort(torch.cat([z, z_out], -1), -1)[0] if with_bg else None
-    density = torch.randn(R, S + O_, generator=g) * 2 if with_bg else None
-    bg_rgb = torch.rand(R, S + O_, 3, generator=g) if with_bg else None
-    inv_s = torch.tensor([20.0])
-    return dict(o=o, d=d, z=z, sample_dist=sample_dist, sdf=sdf, grad=grad, rgb=rgb, z_feed=z_feed, density=density,
-                bg_rgb=bg_rgb, inv_s=inv_s)
 
 
 @pytest.mark.parametrize("S,O_,with_bg,brgb", [(128, 4, True, True), (24, 4, True, False), (32, 0, False, True),

@@ -1,0 +1,333 @@
+"""The per-ray sampler and compositor kernels (csrc/ncw_rays.hip, both objects: the standard one up to 512 samples per ray, the
+large-ray one -DNCW_RAYS_BIG up to 1088) called directly at their shape edges and down the branches no render reaches.
+
+References, cases and the bound are in tests/_ray_cases.py: oracle/neuconw_oracle.py in float64 arbitrates; the same in float32
+on the CPU is the "fp32 restatement"; every comparison asserts err_kernel <= max(floor, 4 * err_fp32_restatement), both errors
+against float64 on the same inputs, and prints the pair (run with -s).  tests/test_ray_cases_host.py checks the cases'
+own conditions without a GPU.
+
+Worst measured pairs, kernel / fp32 restatement, both against float64, on an MI355X (every kernel follows the restatement to
+well inside the factor 4; the worst ratio to its bound anywhere is 0.30):
+  composite_fwd   standard   color_bg 9.1e-06 / 8.2e-06 at (512, 0);  depth 2.5e-03 / 2.5e-03 at (1, 1): one alpha of 1e-5 size
+                  large-ray  color_bg 1.9e-05 / 1.9e-05 at (1056, 32);  weights 1.6e-05 / 1.8e-05 at (1024, 32)
+  composite_bwd   standard   d_inv_s 3.9e-04 / 3.2e-04 at (2, 0);  at S = 1 and at (61, 4) with inv_s = 3000 fp32 cannot resolve
+                             d_sdf / d_inv_s at all (1.2 / 1.2, saturated sigmoids: test_ray_cases_host.py lists these)
+                  large-ray  d_inv_s 1.5e-03 / 1.5e-03 at (509, 4) with cos_anneal = 0, 3.1e-04 / 3.5e-04 at (1056, 32):
+                             a cancelling sum;  d_sdf 1.0e-04 / 1.0e-04 at (509, 4) with inv_s = 3000 and the value switches;
+                             every other adjoint at or below 1.6e-05 / 1.9e-05
+  sample_coarse   standard   1.8e-07 / 1.8e-07 (n = 1)          large-ray  1.5e-07 / 1.5e-07 (n = 513)
+  boundary                   6.1e-08 / 7.0e-08 (n = 24, nb = 65)
+  upsample        standard   2.6e-06 / 2.6e-06 at (3, 5, 64)    large-ray  5.1e-06 / 1.8e-05 at (512, 128, 1024)
+  sort_merge                 exact, both objects
+"""
+import pytest
+import torch
+
+from tests import _ray_cases as C
+from tests._util import rel_err
+
+pytestmark = pytest.mark.gpu
+
+
+def _cu(*ts):
+    return [t.cuda() if t is not None else None for t in ts]
+
+
+def _cpu(d):
+    return {k: v.cpu() for k, v in d.items() if v is not None}
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# compositor
+# --------------------------------------------------------------------------------------------------------------------
+def _run_comp(I, c, cos=None, grad_scale=1.0, grad_scale_dev=None):
+    """One forward + backward of the compositor kernels on inputs I -> (forward, adjoints) on the CPU under the reference's names;
+    d_inv_s stays per ray (key "inv_s_rays") next to its sum over rays (key "inv_s")."""
+    from neuralrecon_w_amd import rayops
+
+    ctx = rayops.CompositeCtx(*_cu(I["o"], I["d"], I["z"], I["sample_dist"], I["sdf"], I["grad"], I["rgb"], I["inv_s"]),
+                              c.cos if cos is None else cos, *_cu(I["z_feed"], I["density"], I["bg_rgb"]),
+                              background_rgb=I["background_rgb"].cuda() if I["background_rgb"] is not None else None,
+                              trim_sphere=c.trim)
+    out = ctx.forward()
+    fwd = _cpu(out)
+    fwd["eik_num"], fwd["eik_den"] = fwd["eik"][0], fwd.pop("eik")[1]
+    if not c.with_bg:
+        fwd.pop("color_bg")  # written as zeros without a background
+    ct = I["cot"]
+    got = ctx.backward(*_cu(ct["d_color"], ct["d_weights_sum"], ct["d_depth"], ct["d_eik_num"]), grad_scale=grad_scale,
+                       grad_scale_dev=grad_scale_dev)
+    adj = {k[2:]: v for k, v in _cpu(got).items()}
+    adj["inv_s_rays"] = adj["inv_s"]
+    adj["inv_s"] = adj["inv_s"].sum().reshape(1)  # per-ray terms: the caller reduces them
+    torch.cuda.synchronize()
+    return fwd, adj
+
+
+def _compare(c, fwd, adj):
+    """Every forward output and adjoint against float64 under the bound; prints the (kernel, restatement) error pairs."""
+    f64, a64, f32, a32 = C.comp_reference(c)
+    assert set(fwd) == set(f64) and set(adj) - {"inv_s_rays"} == set(a64)
+    bad, line = [], []
+    for kind, got, r64, r32 in (("fwd", fwd, f64, f32), ("adj", adj, a64, a32)):
+        for k in r64:
+            assert bool(torch.isfinite(got[k]).all()), (kind, k)
+            e = rel_err(got[k].reshape(r64[k].shape), r64[k])
+            e32 = rel_err(r32[k], r64[k])
+            b = C.bound(C.FLOOR_ADJ if kind == "adj" else C.fwd_floor(k), e32)
+            line.append("%s.%s %.1e/%.1e" % (kind, k, e, e32))
+            if not e <= b:
+                bad.append((kind, k, e, e32, b))
+    print("\n%s [%s]: kernel/fp32: %s" % (C.case_id(c), "large-ray" if c.S + c.O > 512 else "standard", " ".join(line)))
+    assert not bad, bad
+
+
+@pytest.mark.parametrize("c", C.shape_cases(), ids=C.case_id)
+def test_composite_shapes(c):
+    """One launch scans three lengths (S for depth and the sphere colour, M = S + O for the merged and background chains) with
+    per = ceil(m / 64) elements per lane: m below 64, on and next to multiples of 64, S and M on opposite sides of one, the
+    capacity of each object (512 / 1088) and the first size of the large-ray object (513).  Pins wave_excl_scan /
+    wave_suffix_excl_sum at every `per`, weights_max over all M columns and bg_alpha."""
+    _compare(c, *_run_comp(C.comp_case_inputs(c), c))
+
+
+@pytest.mark.parametrize("c", [c for c in C.option_cases() if c.trim], ids=C.case_id)
+def test_composite_options(c):
+    """Branches of composite_fwd_kernel / composite_bwd_kernel by option, at (61, 4) and (509, 4):
+    background_rgb null (`if (A.background_rgb)` in both kernels: colour and the d_wsum correction);  cos_anneal 0 and 1
+    (iter_cos_of and the two step functions of dtc);  inv_s 403 and 3000 (saturated sigmoid_acc, `raw` at its clip);  the value
+    switches at once: density beyond +-20 (`den > 20.f` in the softplus forward and `sg = 1` backward), a grad = 0 column
+    (`gn > 0.f` in the eikonal adjoint), a ray with no sample inside the sphere (every `ins` false: weights_sum 0, the background
+    takes every column), a ray with sdf = -0.5 (pc = nc = 0 at inv_s 3000);  d_depth / d_eik_num = None (zero cotangents)."""
+    _compare(c, *_run_comp(C.comp_case_inputs(c), c))
+
+
+@pytest.mark.parametrize("S,O_", C.OPTION_SHAPES)
+def test_trim_sphere_off_changes_color_bg_only(S, O_):
+    """`if (A.trim_sphere && j < S && inside)` of the background-only chain: trim_sphere = 0 keeps the background alpha of the
+    samples inside the sphere.  color_bg follows the oracle either way and differs between the two; nothing else may move."""
+    ct, cf = C.comp_case(S, O_, trim=True), C.comp_case(S, O_, trim=False)
+    ft, at = _run_comp(C.comp_case_inputs(ct), ct)
+    ff, af = _run_comp(C.comp_case_inputs(cf), cf)
+    _compare(cf, ff, af)
+    assert rel_err(ff["color_bg"], ft["color_bg"]) > 1e-2
+    for k in ft:
+        if k != "color_bg":
+            assert torch.equal(ft[k], ff[k]), k
+    for k in at:
+        assert torch.equal(at[k], af[k]), k
+
+
+@pytest.mark.parametrize("S,O_", C.OPTION_SHAPES)
+@pytest.mark.parametrize("cos", [0.0, 0.3, 1.0])
+def test_cos_anneal_device_scalar(S, O_, cos):
+    """`A.cos_anneal_dev ? A.cos_anneal_dev[0] : A.cos_anneal` (forward and backward): the 1-element device tensor gives bit for
+    bit what the float gives."""
+    c = C.comp_case(S, O_, cos=cos)
+    I = C.comp_case_inputs(c)
+    f0, a0 = _run_comp(I, c)
+    f1, a1 = _run_comp(I, c, cos=torch.tensor([cos], device="cuda"))
+    for k in f0:
+        assert torch.equal(f0[k], f1[k]), k
+    for k in a0:
+        assert torch.equal(a0[k], a1[k]), k
+
+
+@pytest.mark.parametrize("c", C.scale_cases(), ids=C.case_id)
+def test_grad_scale_and_device_scale(c):
+    """`gs = grad_scale_dev ? grad_scale * grad_scale_dev[0] : grad_scale` of composite_bwd_kernel: grad_scale = 4 with
+    grad_scale_dev = 0.5 scales every upstream cotangent by 2 on load, a power of two: every adjoint is bit for bit 2 x the
+    unscaled one (and 4 x with grad_scale alone).  On the plain inputs, where no intermediate is subnormal -- with the value
+    switches on at S = 509 the fp32 restatement itself is not scale-exact (tests/_ray_cases.py: scale_cases)."""
+    I = C.comp_case_inputs(c)
+    _, a1 = _run_comp(I, c)
+    _, a2 = _run_comp(I, c, grad_scale=4.0, grad_scale_dev=torch.tensor([0.5], device="cuda"))
+    _, a4 = _run_comp(I, c, grad_scale=4.0)
+    for k in a1:
+        if k == "inv_s":  # the host-side sum of the per-ray terms (inv_s_rays is compared)
+            continue
+        assert bool(a1[k].abs().max() > 0), k
+        assert torch.equal(a2[k], 2.0 * a1[k]), k
+        assert torch.equal(a4[k], 4.0 * a1[k]), k
+
+
+@pytest.mark.parametrize("c", C.indep_cases(), ids=C.case_id)
+def test_composite_rays_independent_and_repeatable(c):
+    """One wave per ray, four rays per workgroup, R = 9 (three workgroups, the last with one ray): a ray run alone gives bit for
+    bit what it gives in the batch -- no LDS row, scan carry or `r >= R` exit leaks between waves -- and a second run of the batch
+    equals the first."""
+    I = C.comp_case_inputs(c)
+    f, a = _run_comp(I, c)
+    _compare(c, f, a)
+    f2, a2 = _run_comp(I, c)
+    for k in f:
+        assert torch.equal(f[k], f2[k]), k
+    for k in a:
+        assert torch.equal(a[k], a2[k]), k
+    for r in range(c.R):
+        fr, ar = _run_comp(C.slice_rays(I, r, r + 1), c)
+        for k in f:
+            assert torch.equal(fr[k], f[k][r:r + 1]), (r, k)
+        for k in a:
+            if k != "inv_s":
+                assert torch.equal(ar[k], a[k][r:r + 1]), (r, k)
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# sample_coarse / boundary
+# --------------------------------------------------------------------------------------------------------------------
+def _check_coarse(K, n, no, tag):
+    from neuralrecon_w_amd import rayops
+
+    got = rayops.sample_coarse(*_cu(K["near"], K["far"], K["s_near"], K["s_far"]), n, no, *_cu(K["rs"], K["ro"]))
+    torch.cuda.synchronize()
+    assert (got[1] is None) == (no == 0)  # n_outside = 0: the wrapper returns None for z_out
+    worst = (0.0, 0.0)
+    for name, g, r64, r32 in zip(("z", "z_out", "sample_dist"), got, K["ref64"], K["ref32"]):
+        if r64 is None:
+            continue
+        assert g.shape == r64.shape
+        e, e32 = rel_err(g.cpu(), r64), rel_err(r32, r64)
+        assert e <= C.bound(C.FLOOR_SAMPLE, e32), (tag, name, e, e32)
+        worst = max(worst, (e, e32))
+    return worst
+
+
+@pytest.mark.parametrize("n", C.COARSE_N)
+def test_sample_coarse_shapes(n):
+    """sample_coarse_kernel's stride loops (64 lanes per ray): n_samples and n_outside below, at and past one trip, steps == 1 of
+    torch_linspace (n = 1, n_outside = 1), no outside samples, the perturbed branch with its neighbour look-ups at both ends, R = 1
+    and R = 5 (a second, partly filled workgroup); n > 512 runs in the large-ray object."""
+    worst = (0.0, 0.0)
+    for no in C.COARSE_OUT:
+        for perturb in (False, True):
+            for R in C.COARSE_R:
+                worst = max(worst, _check_coarse(C.coarse_case(R, n, no, perturb), n, no, (n, no, perturb, R)))
+    print("\nsample_coarse n=%d [%s]: kernel/fp32 %.1e/%.1e" % (n, "large-ray" if n > 512 else "standard", *worst))
+
+
+@pytest.mark.parametrize("n", [65, 513])
+def test_sample_coarse_window(n):
+    """The fine-octree case: s_near / s_far differ from near / far -- z and sample_dist come from the window, z_out from the
+    ray's far (`fr / zo`)."""
+    w = _check_coarse(C.coarse_case(5, n, 4, True, window=True), n, 4, ("window", n))
+    print("\nsample_coarse window n=%d: kernel/fp32 %.1e/%.1e" % (n, *w))
+
+
+@pytest.mark.parametrize("n", C.BOUNDARY_N)
+@pytest.mark.parametrize("nb", C.BOUNDARY_NB)
+def test_boundary_vs_oracle(n, nb):
+    """boundary_kernel: nb // 2 samples in [near, z_first), the rest in (z_last, far]; nb = 1 has no near part, nb > 64 takes a
+    second trip of the stride loop.  Then the merge the renderer does with them: sort_merge(zb, z) equals the sorted
+    concatenation of the kernel's own two operands exactly (n = 600 with nb = 130: 730 elements, the large-ray object)."""
+    from neuralrecon_w_amd import rayops
+
+    B = C.boundary_case(n, nb)
+    near, far, z = _cu(B["near"], B["far"], B["z"])
+    zb = rayops.boundary(near, far, z, nb)
+    e, e32 = rel_err(zb.cpu(), B["ref64"]), rel_err(B["ref32"], B["ref64"])
+    print("\nboundary n=%d nb=%d: kernel/fp32 %.1e/%.1e" % (n, nb, e, e32))
+    assert zb.shape == (5, nb) and e <= C.bound(C.FLOOR_SAMPLE, e32), (e, e32)
+    merged, _ = rayops.sort_merge(zb, z)
+    assert torch.equal(merged.cpu(), torch.sort(torch.cat([zb.cpu(), B["z"]], -1), dim=-1, stable=True)[0])
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# upsample
+# --------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("n,n_new,inv_s", C.UPSAMPLE_SHAPES)
+def test_upsample_shapes(n, n_new, inv_s):
+    """upsample_kernel: m = n - 1 sections and the m + 1 = n slot CDF scan on both sides of multiples of 64, the smallest ray
+    (n = 2), n_new = 1 (steps == 1 of torch_linspace) and n_new past one trip; 511 is the standard object's capacity, 512 the
+    large-ray object's first size, 1087 its capacity.  Per ray against float64; a ray is left out exactly where the fp32
+    restatement itself is off (sample_pdf's denominator switch at 1e-5, decided in tests/_ray_cases.py); sortedness holds on all."""
+    from neuralrecon_w_amd import rayops
+
+    U = C.upsample_case(n, n_new, inv_s)
+    got = rayops.upsample(*_cu(U["o"], U["d"], U["z"], U["sdf"]), n_new, inv_s).cpu()
+    assert got.shape == (C.UPSAMPLE_R, n_new) and bool(torch.isfinite(got).all())
+    e, e32 = C.upsample_err(got, U), C.upsample_err(U["ref32"], U)
+    print("\nupsample (%d, %d, %g) [%s]: kernel/fp32 %.1e/%.1e, %d rays excluded"
+          % (n, n_new, inv_s, "large-ray" if n > 511 else "standard", e, e32, int(U["excluded"].sum())))
+    assert e <= C.bound(C.FLOOR_UPSAMPLE, e32), (e, e32)
+    assert bool((got[:, 1:] >= got[:, :-1]).all())
+
+
+@pytest.mark.parametrize("n,n_new,inv_s", C.UPSAMPLE_INDEP)
+def test_upsample_rays_independent_and_repeatable(n, n_new, inv_s):
+    """upsample_kernel keeps four rays per workgroup in LDS rows sm[wv]: a ray run alone (R = 1) gives bit for bit what it gives
+    among nine (three workgroups, the last with one ray: the `r >= R` exit), and a second run equals the first; both objects."""
+    from neuralrecon_w_amd import rayops
+
+    U = C.upsample_case(n, n_new, inv_s)
+    a = [t[:9] for t in _cu(U["o"], U["d"], U["z"], U["sdf"])]
+    got = rayops.upsample(*a, n_new, inv_s)
+    assert torch.equal(got, rayops.upsample(*a, n_new, inv_s))
+    for r in range(9):
+        assert torch.equal(rayops.upsample(*[t[r:r + 1] for t in a], n_new, inv_s), got[r:r + 1]), r
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# sort_merge
+# --------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("na,nb", C.MERGE_SHAPES)
+def test_sort_merge_shapes(na, nb):
+    """sort_merge_kernel's rank by counting: an empty operand, one element, a full trip, the capacity of each object; b unsorted,
+    ties within and across the operands (`w == v && j < i`), both signs; with and without the payload (`if (pout)`).  Exact
+    equality with the stable torch.sort and the payload gathered alike."""
+    from neuralrecon_w_amd import rayops
+
+    M = C.merge_case(na, nb)
+    a, b, pa, pb = _cu(M["a"], M["b"], M["pa"], M["pb"])
+    out, pout = rayops.sort_merge(a, b, pa, pb)
+    assert torch.equal(out.cpu(), M["ref"]) and torch.equal(pout.cpu(), M["ref_payload"])
+    out2, none = rayops.sort_merge(a, b)
+    assert none is None and torch.equal(out2.cpu(), M["ref"])
+
+
+@pytest.mark.parametrize("na,nb", C.MERGE_INDEP)
+def test_sort_merge_rays_independent_and_repeatable(na, nb):
+    """sort_merge_kernel, the same: one LDS row per wave, nine rays against each alone, and a repeated run; both objects."""
+    from neuralrecon_w_amd import rayops
+
+    M = C.merge_case(na, nb, R=9)
+    a, b, pa, pb = _cu(M["a"], M["b"], M["pa"], M["pb"])
+    out, pout = rayops.sort_merge(a, b, pa, pb)
+    out2, pout2 = rayops.sort_merge(a, b, pa, pb)
+    assert torch.equal(out, out2) and torch.equal(pout, pout2)
+    for r in range(9):
+        o1, p1 = rayops.sort_merge(*[t[r:r + 1] for t in (a, b, pa, pb)])
+        assert torch.equal(o1, out[r:r + 1]) and torch.equal(p1, pout[r:r + 1]), r
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# argument checks: each of these returns NCW_E_BADARG in csrc/ncw_rays.hip before any launch (the size is neither taken by the
+# standard object nor forwarded to the large-ray one), so no kernel ever sees an over-long ray
+# --------------------------------------------------------------------------------------------------------------------
+def test_bad_sizes_raise():
+    import neuralrecon_w_amd as nw
+    from neuralrecon_w_amd import rayops
+
+    dev = "cuda"
+    o = torch.zeros(2, 3, device=dev)
+    for n in (1, 1088):  # ncw_upsample: n < 2, n > RAY_MAXN_BIG - 1
+        with pytest.raises(nw.NeuconwHipError):
+            rayops.upsample(o, o, torch.zeros(2, n, device=dev), torch.zeros(2, n, device=dev), 4, 64.0)
+    near, far = torch.ones(2, 1, device=dev), torch.full((2, 1), 3.0, device=dev)
+    for n in (0, 1089):  # ncw_sample_coarse: n_samples < 1, > RAY_MAXN_BIG
+        with pytest.raises(nw.NeuconwHipError):
+            rayops.sample_coarse(near, far, near, far, n, 4)
+    with pytest.raises(nw.NeuconwHipError):  # ncw_sort_merge: na + nb > RAY_MAXN_BIG
+        rayops.sort_merge(torch.zeros(2, 1000, device=dev), torch.zeros(2, 89, device=dev))
+    e = lambda *s: torch.zeros(*s, device=dev)  # noqa: E731
+    long_ray = {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in C.comp_inputs(2, 1057, 32, 3).items()}
+    no_sample = dict(o=o, d=o, z=e(2, 0), sample_dist=e(2, 1), sdf=e(2, 0), grad=e(2, 0, 3), rgb=e(2, 0, 3), inv_s=e(1) + 20,
+                     z_feed=None, density=None, bg_rgb=None)
+    for I in (long_ray, no_sample):  # ncw_composite_fwd / _bwd: M = 1089 > RAY_MAXN_BIG, S = 0 < 1
+        ctx = rayops.CompositeCtx(I["o"], I["d"], I["z"], I["sample_dist"], I["sdf"], I["grad"], I["rgb"], I["inv_s"], 0.3,
+                                  I["z_feed"], I["density"], I["bg_rgb"])
+        with pytest.raises(nw.NeuconwHipError):
+            ctx.forward()
+        with pytest.raises(nw.NeuconwHipError):
+            ctx.backward(torch.zeros(2, 3, device=dev), torch.zeros(2, device=dev), None, None)
+    torch.cuda.synchronize()
