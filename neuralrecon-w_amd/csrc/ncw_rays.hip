@@ -8,26 +8,19 @@
 //   ncw_sort_merge      renderer.py:343-363 (cat_z_vals), :566, :835-836
 //   ncw_boundary        renderer.py:549-565
 //   ncw_composite_fwd / _bwd   renderer.py:205-216 (bg alpha), :586-783 (render_core tail)
+// and, further down, the kernels around them that keep no ray in LDS:
+//   ncw_ray_sum_rows, ncw_scatter_add_rows   per-ray sum / embedding scatter of the appearance-code adjoints
+//   ncw_batch_assemble                       a training batch gathered from the HBM-resident ray cache
+//   ncw_ray_tail_fwd / _bwd                  the per-ray loss terms render() returns
+//   ncw_bg_select                            which samples need the background NeRF at all
 #include "../../include/neuconw_hip.h"
 #include "ncw_common.h"
 
-// A ray's samples live in LDS (one wave per ray).  The file is compiled TWICE (neuralrecon-w_amd/build.py): the standard object
-// handles up to 512 samples per ray (two workgroups per CU in the compositor backward) and forwards larger rays -- up to 1088: the
-// reference's own defaults, config/defaults.py:8-9,32: 512 + 512 samples + 32 outside -- to the `_big` entry points of the second
-// object (-DNCW_RAYS_BIG: the same kernels with 17 elements per lane, 122 KB of LDS in the compositor backward).
-#ifdef NCW_RAYS_BIG
-#define RAY_MAXN 1088
-#define NCW_RAYNS ncw_rays_big
-#define NCW_RAYFN(name) name##_big
-#else
-#define RAY_MAXN 512            // max samples per ray handled in LDS by this object
-#define NCW_RAYNS ncw_rays_std
-#define NCW_RAYFN(name) name
-#endif
-#define RAY_MAXN_BIG 1088
-#define RAY_CH (RAY_MAXN / 64)  // elements per lane in a chunked scan
-
-namespace NCW_RAYNS {
+// A ray's samples live in LDS (one wave per ray), so the four kernels that keep them there are templates on the capacity MAXN
+// and exist twice: 512 samples per ray (two workgroups per CU in the compositor backward) and 1088 -- the reference's own
+// defaults, config/defaults.py:8-9,32: 512 + 512 samples + 32 outside -- with 17 elements per lane in a scan and 122 KB of LDS in
+// the compositor backward.  Each entry point picks the smallest capacity its ray fits (ray_capacity) or returns NCW_E_BADARG.
+constexpr int RAY_CAP_SMALL = 512, RAY_CAP_LARGE = 1088;
 
 NCW_DEV float sigmoid_acc(float x) { return 1.f / (1.f + expf(-x)); }
 
@@ -39,15 +32,15 @@ NCW_DEV float torch_linspace(float start, float end, int steps, int i) {
 }
 
 // Exclusive scan over a[0..m) in LDS (one wave), op = multiply (MUL) or add; out may alias a.
-// Returns the total (product / sum of all m elements) in every lane.
-template <bool MUL>
+// Returns the total (product / sum of all m elements) in every lane.  CH = MAXN / 64: elements per lane.
+template <bool MUL, int CH>
 NCW_DEV float wave_excl_scan(const float* a, float* out, int m, int lane) {
     const int per = (m + 63) >> 6;
     const int b = lane * per;
-    float loc[RAY_CH];
+    float loc[CH];
     float tot = MUL ? 1.f : 0.f;
 #pragma unroll
-    for (int k = 0; k < RAY_CH; ++k) {
+    for (int k = 0; k < CH; ++k) {
         if (k < per) {
             const int i = b + k;
             loc[k] = (i < m) ? a[i] : (MUL ? 1.f : 0.f);
@@ -66,7 +59,7 @@ NCW_DEV float wave_excl_scan(const float* a, float* out, int m, int lane) {
     const float total = __shfl(inc, 63, 64);
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
-    for (int k = 0; k < RAY_CH; ++k) {
+    for (int k = 0; k < CH; ++k) {
         if (k < per) {
             const int i = b + k;
             if (i < m) out[i] = run;
@@ -81,6 +74,64 @@ NCW_DEV float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The formulas the kernels below share, each stated once.
+// ------------------------------------------------------------------------------------------------
+struct Ray { float ox, oy, oz, dx, dy, dz; };
+
+NCW_DEV Ray load_ray(const float* rays_o, const float* rays_d, int r) {
+    return {rays_o[r * 3], rays_o[r * 3 + 1], rays_o[r * 3 + 2], rays_d[r * 3], rays_d[r * 3 + 1], rays_d[r * 3 + 2]};
+}
+
+// |o + d t|
+NCW_DEV float ray_radius(const Ray& y, float t) {
+    const float px = y.ox + y.dx * t, py = y.oy + y.dy * t, pz = y.oz + y.dz * t;
+    return sqrtf(px * px + py * py + pz * pz);
+}
+
+// Section i of a row z[0..n) of sorted samples: its length (the last one ends `sdist` further) and its mid-point.
+struct Section { float dist, mid; };
+
+NCW_DEV Section section_of(const float* z, int i, int n, float sdist) {
+    const float zi = z[i];
+    const float dist = (i + 1 < n) ? z[i + 1] - zi : sdist;
+    return {dist, zi + dist * 0.5f};
+}
+
+// inside_sphere (renderer.py:637) of a section of the PRIMARY z, from the radius of its mid-point: what the compositor masks its
+// alpha with, forward and backward, and what ncw_bg_select leaves out
+NCW_DEV bool inside_sphere(float radius) { return radius < 1.0f; }
+NCW_DEV bool section_inside(const Ray& y, const float* z, int i, int n, float sdist) {
+    return inside_sphere(ray_radius(y, section_of(z, i, n, sdist).mid));
+}
+
+// NeuS alpha of a section (renderer.py:300-318, 618-635): the sdf at its two ends estimated as sdf -+ cs dist / 2 (the sigmoid
+// arguments ep, en before the factor inv_s), pc / nc their sigmoids, raw = the un-clamped alpha
+struct NeusAlpha { float ep, en, pc, nc, raw; };
+
+NCW_DEV NeusAlpha neus_alpha(float sdf, float cs, float dist, float inv_s) {
+    NeusAlpha a;
+    a.ep = sdf - cs * dist * 0.5f;
+    a.en = sdf + cs * dist * 0.5f;
+    a.pc = sigmoid_acc(a.ep * inv_s);
+    a.nc = sigmoid_acc(a.en * inv_s);
+    a.raw = (a.pc - a.nc + 1e-5f) / (a.pc + 1e-5f);
+    return a;
+}
+
+NCW_DEV float clamp01(float x) { return fminf(fmaxf(x, 0.f), 1.f); }
+
+// background alpha of a section (renderer.py:205-207): 1 - exp(-softplus(den) dist), F.softplus with its threshold 20 ...
+NCW_DEV float bg_alpha_of(float den, float dist) {
+    const float sp = den > 20.f ? den : log1pf(expf(den));
+    return 1.0f - expf(-sp * dist);
+}
+// ... and its adjoint: d alpha / d den = exp(-sp dist) dist sigmoid(den) = (1 - alpha) dist sigmoid(den)
+NCW_DEV float bg_alpha_bwd(float dalpha, float alpha, float den, float dist) {
+    const float sg = den > 20.f ? 1.f : sigmoid_acc(den);
+    return dalpha * (1.0f - alpha) * dist * sg;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -121,11 +172,13 @@ __global__ void sample_coarse_kernel(const float* __restrict__ near, const float
 // ------------------------------------------------------------------------------------------------
 // up_sample + sample_pdf(det=True)
 // ------------------------------------------------------------------------------------------------
+template <int MAXN>
 __global__ __launch_bounds__(256) void upsample_kernel(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
                                                        const float* __restrict__ z, const float* __restrict__ sdf,
                                                        int R, int n, float inv_s, int n_new,
                                                        float* __restrict__ z_new) {
-    __shared__ float sm[4][4][RAY_MAXN];
+    constexpr int CH = MAXN / 64;
+    __shared__ float sm[4][4][MAXN];
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + wv;
     if (r >= R) return;
@@ -133,22 +186,20 @@ __global__ __launch_bounds__(256) void upsample_kernel(const float* __restrict__
     float* sd = sm[wv][1];
     float* t0 = sm[wv][2];  // radius -> cos -> alpha -> cdf
     float* t1 = sm[wv][3];
-    const float ox = rays_o[r * 3], oy = rays_o[r * 3 + 1], oz = rays_o[r * 3 + 2];
-    const float dx = rays_d[r * 3], dy = rays_d[r * 3 + 1], dz = rays_d[r * 3 + 2];
+    const Ray y = load_ray(rays_o, rays_d, r);
     const int m = n - 1;
     for (int i = lane; i < n; i += 64) {
         const float zz = z[(size_t)r * n + i];
         zs[i] = zz;
         sd[i] = sdf[(size_t)r * n + i];
-        const float px = ox + dx * zz, py = oy + dy * zz, pz = oz + dz * zz;
-        t0[i] = sqrtf(px * px + py * py + pz * pz);
+        t0[i] = ray_radius(y, zz);
     }
     __builtin_amdgcn_wave_barrier();
     for (int i = lane; i < m; i += 64) t1[i] = (sd[i + 1] - sd[i]) / (zs[i + 1] - zs[i] + 1e-5f);
     __builtin_amdgcn_wave_barrier();
-    float alpha_l[RAY_CH];
+    float alpha_l[CH];
 #pragma unroll
-    for (int k = 0; k < RAY_CH; ++k) {
+    for (int k = 0; k < CH; ++k) {
         const int i = lane + 64 * k;
         alpha_l[k] = 0.f;
         if (i < m) {
@@ -157,24 +208,20 @@ __global__ __launch_bounds__(256) void upsample_kernel(const float* __restrict__
             cv = fminf(fmaxf(cv, -1e3f), 0.f);
             const bool inside = (t0[i] < 1.0f) || (t0[i + 1] < 1.0f);
             cv = inside ? cv : 0.f;
-            const float mid = (sd[i] + sd[i + 1]) * 0.5f;
-            const float dist = zs[i + 1] - zs[i];
-            const float pe = mid - cv * dist * 0.5f, ne = mid + cv * dist * 0.5f;
-            const float pc = sigmoid_acc(pe * inv_s), nc = sigmoid_acc(ne * inv_s);
-            alpha_l[k] = (pc - nc + 1e-5f) / (pc + 1e-5f);
+            alpha_l[k] = neus_alpha((sd[i] + sd[i + 1]) * 0.5f, cv, zs[i + 1] - zs[i], inv_s).raw;
         }
     }
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
-    for (int k = 0; k < RAY_CH; ++k) {
+    for (int k = 0; k < CH; ++k) {
         const int i = lane + 64 * k;
         if (i < m) t0[i] = 1.0f - alpha_l[k] + 1e-7f;
     }
     __builtin_amdgcn_wave_barrier();
-    wave_excl_scan<true>(t0, t0, m, lane);  // t0 = T_i
+    wave_excl_scan<true, CH>(t0, t0, m, lane);  // t0 = T_i
     float wsum = 0.f;
 #pragma unroll
-    for (int k = 0; k < RAY_CH; ++k) {
+    for (int k = 0; k < CH; ++k) {
         const int i = lane + 64 * k;
         if (i < m) {
             const float w = alpha_l[k] * t0[i] + 1e-5f;  // sample_pdf: weights + 1e-5
@@ -189,7 +236,7 @@ __global__ __launch_bounds__(256) void upsample_kernel(const float* __restrict__
     // cdf[0] = 0, cdf[i+1] = inclusive cumsum -> exclusive scan over m+1 slots of [pdf..., x]
     if (lane == 0) t1[m] = 0.f;
     __builtin_amdgcn_wave_barrier();
-    wave_excl_scan<false>(t1, t0, m + 1, lane);  // t0[0..n) = cdf
+    wave_excl_scan<false, CH>(t1, t0, m + 1, lane);  // t0[0..n) = cdf
     for (int j = lane; j < n_new; j += 64) {
         const float u = torch_linspace(0.5f / (float)n_new, 1.0f - 0.5f / (float)n_new, n_new, j);
         int lo = 0, hi = n;  // count of cdf entries <= u  (searchsorted right=True)
@@ -209,11 +256,12 @@ __global__ __launch_bounds__(256) void upsample_kernel(const float* __restrict__
 // ------------------------------------------------------------------------------------------------
 // stable sort of cat([a, b]) per ray with an optional payload (sdf) -- rank by counting in LDS.
 // ------------------------------------------------------------------------------------------------
+template <int MAXN>
 __global__ __launch_bounds__(256) void sort_merge_kernel(const float* __restrict__ a, int na, const float* __restrict__ b,
                                                          int nb, const float* __restrict__ pa,
                                                          const float* __restrict__ pb, int R, float* __restrict__ out,
                                                          float* __restrict__ pout) {
-    __shared__ float sm[4][RAY_MAXN];
+    __shared__ float sm[4][MAXN];
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + wv;
     if (r >= R) return;
@@ -251,24 +299,14 @@ __global__ void boundary_kernel(const float* __restrict__ near, const float* __r
 // ------------------------------------------------------------------------------------------------
 // Compositor forward.  Per ray: S inside samples (+ O outside, bg arrays have S+O columns).
 // ------------------------------------------------------------------------------------------------
-struct CompArgs {
-    const float *rays_o, *rays_d, *z, *z_feed, *sample_dist, *sdf, *grad, *rgb, *density, *bg_rgb, *inv_s;
-    const float* background_rgb;  // [3] or null
-    const float* cos_anneal_dev;  // [1] or null
-    float cos_anneal;
-    int R, S, O, has_bg, trim_sphere;
-};
-struct CompOut {
-    float *color, *color_sphere, *color_bg, *weights, *weights_sum, *cdf, *inside, *depth, *normals, *eik;
-    float *mid_z, *dists, *bg_alpha, *weights_max;
-};
-
 NCW_DEV float iter_cos_of(float tc, float c) {
     return -(fmaxf(-tc * 0.5f + 0.5f, 0.f) * (1.0f - c) + fmaxf(-tc, 0.f) * c);
 }
 
-__global__ __launch_bounds__(256) void composite_fwd_kernel(CompArgs A, CompOut Q) {
-    __shared__ float sm[4][4][RAY_MAXN];
+template <int MAXN>
+__global__ __launch_bounds__(256) void composite_fwd_kernel(NcwCompositeIn A, NcwCompositeOut Q) {
+    constexpr int CH = MAXN / 64;
+    __shared__ float sm[4][4][MAXN];
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + wv;
     if (r >= A.R) return;
@@ -277,34 +315,25 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(CompArgs A, CompOut 
     float* alm = sm[wv][1];  // merged alpha
     float* tA = sm[wv][2];
     float* tB = sm[wv][3];
-    const float ox = A.rays_o[r * 3], oy = A.rays_o[r * 3 + 1], oz = A.rays_o[r * 3 + 2];
-    const float dx = A.rays_d[r * 3], dy = A.rays_d[r * 3 + 1], dz = A.rays_d[r * 3 + 2];
+    const Ray y = load_ray(A.rays_o, A.rays_d, r);
     const float inv_s = A.inv_s[0], sdist = A.sample_dist[r];
     const float* zr = A.z + (size_t)r * S;
     float eik_num = 0.f, eik_den = 0.f;
     // ---- per-sample quantities -------------------------------------------------------------
     for (int i = lane; i < S; i += 64) {
-        const float zi = zr[i];
-        const float dist = (i + 1 < S) ? zr[i + 1] - zi : sdist;
-        const float mid = zi + dist * 0.5f;
-        const float px = ox + dx * mid, py = oy + dy * mid, pz = oz + dz * mid;
-        const float pn = sqrtf(px * px + py * py + pz * pz);
+        const Section sec = section_of(zr, i, S, sdist);
+        const float pn = ray_radius(y, sec.mid);
         const size_t q = (size_t)r * S + i;
         const float gx = A.grad[q * 3], gy = A.grad[q * 3 + 1], gz = A.grad[q * 3 + 2];
-        const float tc = dx * gx + dy * gy + dz * gz;
+        const float tc = y.dx * gx + y.dy * gy + y.dz * gz;
         const float ic = iter_cos_of(tc, A.cos_anneal_dev ? A.cos_anneal_dev[0] : A.cos_anneal);
-        const float sd = A.sdf[q];
-        const float en = sd + ic * dist * 0.5f, ep = sd - ic * dist * 0.5f;
-        const float pc = sigmoid_acc(ep * inv_s), nc = sigmoid_acc(en * inv_s);
-        float al = (pc - nc + 1e-5f) / (pc + 1e-5f);
-        al = fminf(fmaxf(al, 0.f), 1.f);
-        const float inside = pn < 1.0f ? 1.f : 0.f;
+        const NeusAlpha na = neus_alpha(A.sdf[q], ic, sec.dist, inv_s);
         const float relax = pn < 1.2f ? 1.f : 0.f;
-        al0[i] = al;
-        Q.cdf[q] = pc;
-        Q.inside[q] = inside;
-        Q.mid_z[q] = mid;
-        Q.dists[q] = dist;
+        al0[i] = clamp01(na.raw);
+        Q.cdf[q] = na.pc;
+        Q.inside[q] = inside_sphere(pn) ? 1.f : 0.f;
+        Q.mid_z[q] = sec.mid;
+        Q.dists[q] = sec.dist;
         const float gn = sqrtf(gx * gx + gy * gy + gz * gz);
         eik_num += relax * (gn - 1.0f) * (gn - 1.0f);
         eik_den += relax;
@@ -313,10 +342,7 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(CompArgs A, CompOut 
     if (A.has_bg) {
         const float* zf = A.z_feed + (size_t)r * M;
         for (int j = lane; j < M; j += 64) {
-            const float dist = (j + 1 < M) ? zf[j + 1] - zf[j] : sdist;
-            const float den = A.density[(size_t)r * M + j];
-            const float sp = den > 20.f ? den : log1pf(expf(den));  // F.softplus, threshold 20
-            const float ba = 1.0f - expf(-sp * dist);
+            const float ba = bg_alpha_of(A.density[(size_t)r * M + j], section_of(zf, j, M, sdist).dist);
             tB[j] = ba;
             Q.bg_alpha[(size_t)r * M + j] = ba;
         }
@@ -325,7 +351,7 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(CompArgs A, CompOut 
     // ---- depth from the un-masked alpha (renderer.py:641, 365-378) ----------------------------
     for (int i = lane; i < S; i += 64) tA[i] = 1.0f - al0[i] + 1e-7f;
     __builtin_amdgcn_wave_barrier();
-    wave_excl_scan<true>(tA, tA, S, lane);
+    wave_excl_scan<true, CH>(tA, tA, S, lane);
     float depth = 0.f;
     for (int i = lane; i < S; i += 64) depth += al0[i] * tA[i] * Q.mid_z[(size_t)r * S + i];
     depth = wave_sum(depth);
@@ -341,7 +367,7 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(CompArgs A, CompOut 
     __builtin_amdgcn_wave_barrier();
     for (int j = lane; j < M; j += 64) tA[j] = 1.0f - alm[j] + 1e-7f;
     __builtin_amdgcn_wave_barrier();
-    wave_excl_scan<true>(tA, tA, M, lane);  // tA = T merged
+    wave_excl_scan<true, CH>(tA, tA, M, lane);  // tA = T merged
     float cr = 0.f, cg = 0.f, cb = 0.f, wsum = 0.f, nx = 0.f, ny = 0.f, nz = 0.f, wmax = -3.4e38f;
     for (int j = lane; j < M; j += 64) {
         const float w = alm[j] * tA[j];
@@ -377,7 +403,7 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(CompArgs A, CompOut 
     // ---- sphere-only colour (renderer.py:735-746) ---------------------------------------------
     for (int i = lane; i < S; i += 64) tA[i] = 1.0f - al0[i] * Q.inside[(size_t)r * S + i] + 1e-7f;
     __builtin_amdgcn_wave_barrier();
-    wave_excl_scan<true>(tA, tA, S, lane);
+    wave_excl_scan<true, CH>(tA, tA, S, lane);
     float sr = 0.f, sg = 0.f, sb = 0.f;
     for (int i = lane; i < S; i += 64) {
         const float ins = Q.inside[(size_t)r * S + i];
@@ -397,7 +423,7 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(CompArgs A, CompOut 
             tA[j] = 1.0f - a + 1e-7f;
         }
         __builtin_amdgcn_wave_barrier();
-        wave_excl_scan<true>(tA, tA, M, lane);
+        wave_excl_scan<true, CH>(tA, tA, M, lane);
         for (int j = lane; j < M; j += 64) {
             const float w = alm[j] * tA[j];
             const size_t q = ((size_t)r * M + j) * 3;
@@ -423,21 +449,15 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(CompArgs A, CompOut 
 // Compositor backward (SURVEY 8a-12 backward contract).  Upstream: d_color[R,3], d_wsum[R],
 // d_depth[R], d_eik_num[R].  Reverse scans:  dL/dalpha_i = T_i wbar_i - (sum_{k>i} w_k wbar_k)/(1-alpha_i+eps)
 // ------------------------------------------------------------------------------------------------
-struct CompBwd {
-    const float *d_color, *d_wsum, *d_depth, *d_eik;
-    float *d_sdf, *d_grad, *d_rgb, *d_density, *d_bg_rgb, *d_inv_s;
-    float grad_scale;  // every upstream cotangent is multiplied by it on load (fp16 loss scaling; a power of two is exact)
-    const float* grad_scale_dev;  // dynamic part of the scale (device scalar) or nullptr
-};
-
 // suffix-exclusive sum: out[i] = sum_{k>i} a[k]
+template <int CH>
 NCW_DEV void wave_suffix_excl_sum(const float* a, float* out, int m, int lane) {
     const int per = (m + 63) >> 6;
     const int b = lane * per;
-    float loc[RAY_CH];
+    float loc[CH];
     float tot = 0.f;
 #pragma unroll
-    for (int k = 0; k < RAY_CH; ++k)
+    for (int k = 0; k < CH; ++k)
         if (k < per) {
             const int i = b + k;
             loc[k] = (i < m) ? a[i] : 0.f;
@@ -453,7 +473,7 @@ NCW_DEV void wave_suffix_excl_sum(const float* a, float* out, int m, int lane) {
     if (lane == 63) run = 0.f;
     __builtin_amdgcn_wave_barrier();
 #pragma unroll
-    for (int k = RAY_CH - 1; k >= 0; --k)
+    for (int k = CH - 1; k >= 0; --k)
         if (k < per) {
             const int i = b + k;
             if (i < m) out[i] = run;
@@ -462,8 +482,10 @@ NCW_DEV void wave_suffix_excl_sum(const float* a, float* out, int m, int lane) {
     __builtin_amdgcn_wave_barrier();
 }
 
-__global__ __launch_bounds__(256) void composite_bwd_kernel(CompArgs A, CompBwd G) {
-    __shared__ float sm[4][5][RAY_MAXN];
+template <int MAXN>
+__global__ __launch_bounds__(256) void composite_bwd_kernel(NcwCompositeIn A, NcwCompositeGrad G) {
+    constexpr int CH = MAXN / 64;
+    __shared__ float sm[4][5][MAXN];
     const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + wv;
     if (r >= A.R) return;
@@ -473,74 +495,49 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(CompArgs A, CompBwd 
     float* T = sm[wv][2];
     float* wk = sm[wv][3];
     float* dal0 = sm[wv][4];  // accumulates dL/d alpha0
-    const float ox = A.rays_o[r * 3], oy = A.rays_o[r * 3 + 1], oz = A.rays_o[r * 3 + 2];
-    const float dx = A.rays_d[r * 3], dy = A.rays_d[r * 3 + 1], dz = A.rays_d[r * 3 + 2];
+    const Ray y = load_ray(A.rays_o, A.rays_d, r);
     const float inv_s = A.inv_s[0], sdist = A.sample_dist[r], c = A.cos_anneal_dev ? A.cos_anneal_dev[0] : A.cos_anneal;
     const float* zr = A.z + (size_t)r * S;
     const float gs = G.grad_scale_dev ? G.grad_scale * G.grad_scale_dev[0] : G.grad_scale;
     const float dcr = G.d_color[r * 3] * gs, dcg = G.d_color[r * 3 + 1] * gs, dcb = G.d_color[r * 3 + 2] * gs;
-    float dws = G.d_wsum[r] * gs;
+    float dws = G.d_weights_sum[r] * gs;
     if (A.background_rgb)
         dws -= dcr * A.background_rgb[0] + dcg * A.background_rgb[1] + dcb * A.background_rgb[2];
-    const float ddep = G.d_depth[r] * gs, deik = G.d_eik[r] * gs;
+    const float ddep = G.d_depth[r] * gs, deik = G.d_eik_num[r] * gs;
     // recompute alpha0, bg alpha
     for (int i = lane; i < S; i += 64) {
-        const float zi = zr[i];
-        const float dist = (i + 1 < S) ? zr[i + 1] - zi : sdist;
         const size_t q = (size_t)r * S + i;
-        const float gx = A.grad[q * 3], gy = A.grad[q * 3 + 1], gz = A.grad[q * 3 + 2];
-        const float tc = dx * gx + dy * gy + dz * gz;
-        const float ic = iter_cos_of(tc, c);
-        const float sd = A.sdf[q];
-        const float pc = sigmoid_acc((sd - ic * dist * 0.5f) * inv_s), nc = sigmoid_acc((sd + ic * dist * 0.5f) * inv_s);
-        const float raw = (pc - nc + 1e-5f) / (pc + 1e-5f);
-        al0[i] = fminf(fmaxf(raw, 0.f), 1.f);
+        const float tc = y.dx * A.grad[q * 3] + y.dy * A.grad[q * 3 + 1] + y.dz * A.grad[q * 3 + 2];
+        al0[i] = clamp01(neus_alpha(A.sdf[q], iter_cos_of(tc, c), section_of(zr, i, S, sdist).dist, inv_s).raw);
         dal0[i] = 0.f;
     }
     __builtin_amdgcn_wave_barrier();
     // ---- chain B: depth ------------------------------------------------------------------
     for (int i = lane; i < S; i += 64) T[i] = 1.0f - al0[i] + 1e-7f;
     __builtin_amdgcn_wave_barrier();
-    wave_excl_scan<true>(T, T, S, lane);
+    wave_excl_scan<true, CH>(T, T, S, lane);
     for (int i = lane; i < S; i += 64) {
-        const float zi = zr[i];
-        const float dist = (i + 1 < S) ? zr[i + 1] - zi : sdist;
-        const float wb = ddep * (zi + dist * 0.5f);
+        const float wb = ddep * section_of(zr, i, S, sdist).mid;
         wk[i] = al0[i] * T[i] * wb;  // w_k * wbar_k
     }
     __builtin_amdgcn_wave_barrier();
-    wave_suffix_excl_sum(wk, wk, S, lane);
+    wave_suffix_excl_sum<CH>(wk, wk, S, lane);
     for (int i = lane; i < S; i += 64) {
-        const float zi = zr[i];
-        const float dist = (i + 1 < S) ? zr[i + 1] - zi : sdist;
-        dal0[i] += T[i] * ddep * (zi + dist * 0.5f) - wk[i] / (1.0f - al0[i] + 1e-7f);
+        const float mid = section_of(zr, i, S, sdist).mid;  // stated before the product: evaluated after T[i] * ddep it fuses differently
+        dal0[i] += T[i] * ddep * mid - wk[i] / (1.0f - al0[i] + 1e-7f);
     }
     __builtin_amdgcn_wave_barrier();
     // ---- chain A: merged alpha -> colour, weights_sum ------------------------------------------
-    float* bga = wk;  // reuse after chain B finished: bg alpha into a private array
-    __shared__ float smb[4][2][RAY_MAXN];
+    __shared__ float smb[4][2][MAXN];
     float* ba = smb[wv][0];
     float* wbar = smb[wv][1];
-    (void)bga;
     if (A.has_bg) {
         const float* zf = A.z_feed + (size_t)r * M;
-        for (int j = lane; j < M; j += 64) {
-            const float dist = (j + 1 < M) ? zf[j + 1] - zf[j] : sdist;
-            const float den = A.density[(size_t)r * M + j];
-            const float sp = den > 20.f ? den : log1pf(expf(den));
-            ba[j] = 1.0f - expf(-sp * dist);
-        }
+        for (int j = lane; j < M; j += 64) ba[j] = bg_alpha_of(A.density[(size_t)r * M + j], section_of(zf, j, M, sdist).dist);
     }
     __builtin_amdgcn_wave_barrier();
     for (int j = lane; j < M; j += 64) {
-        bool ins = false;
-        if (j < S) {
-            const float zi = zr[j];
-            const float dist = (j + 1 < S) ? zr[j + 1] - zi : sdist;
-            const float mid = zi + dist * 0.5f;
-            const float px = ox + dx * mid, py = oy + dy * mid, pz = oz + dz * mid;
-            ins = sqrtf(px * px + py * py + pz * pz) < 1.0f;
-        }
+        const bool ins = j < S && section_inside(y, zr, j, S, sdist);
         const float a = ins ? al0[j] : (A.has_bg ? ba[j] : 0.f);
         alm[j] = a;
         T[j] = 1.0f - a + 1e-7f;
@@ -555,23 +552,16 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(CompArgs A, CompBwd 
         wbar[j] = dcr * rr + dcg * gg + dcb * bb + (ins ? dws : 0.f);
     }
     __builtin_amdgcn_wave_barrier();
-    wave_excl_scan<true>(T, T, M, lane);
+    wave_excl_scan<true, CH>(T, T, M, lane);
     for (int j = lane; j < M; j += 64) wk[j] = alm[j] * T[j] * wbar[j];
     __builtin_amdgcn_wave_barrier();
     float* suf = wk;
     // keep w (for d_rgb) before overwriting: recompute from alm*T
-    wave_suffix_excl_sum(wk, suf, M, lane);
+    wave_suffix_excl_sum<CH>(wk, suf, M, lane);
     for (int j = lane; j < M; j += 64) {
         const float w = alm[j] * T[j];
         const float dalpha = T[j] * wbar[j] - suf[j] / (1.0f - alm[j] + 1e-7f);
-        bool ins = false;
-        if (j < S) {
-            const float zi = zr[j];
-            const float dist = (j + 1 < S) ? zr[j + 1] - zi : sdist;
-            const float mid = zi + dist * 0.5f;
-            const float px = ox + dx * mid, py = oy + dy * mid, pz = oz + dz * mid;
-            ins = sqrtf(px * px + py * py + pz * pz) < 1.0f;
-        }
+        const bool ins = j < S && section_inside(y, zr, j, S, sdist);
         if (j < S) {
             const size_t q = ((size_t)r * S + j) * 3;
             G.d_rgb[q] = ins ? dcr * w : 0.f;
@@ -584,34 +574,24 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(CompArgs A, CompBwd 
             G.d_bg_rgb[q] = ins ? 0.f : dcr * w;
             G.d_bg_rgb[q + 1] = ins ? 0.f : dcg * w;
             G.d_bg_rgb[q + 2] = ins ? 0.f : dcb * w;
-            // bg_alpha = 1 - exp(-softplus(den) dist): d/d den = exp(-sp dist) dist sigmoid(den)
             const float* zf = A.z_feed + (size_t)r * M;
-            const float dist = (j + 1 < M) ? zf[j + 1] - zf[j] : sdist;
-            const float den = A.density[(size_t)r * M + j];
-            const float sg = den > 20.f ? 1.f : sigmoid_acc(den);
-            const float dba = ins ? 0.f : dalpha;
-            G.d_density[(size_t)r * M + j] = dba * (1.0f - ba[j]) * dist * sg;
+            G.d_density[(size_t)r * M + j] =
+                bg_alpha_bwd(ins ? 0.f : dalpha, ba[j], A.density[(size_t)r * M + j], section_of(zf, j, M, sdist).dist);
         }
     }
     __builtin_amdgcn_wave_barrier();
     // ---- through alpha0 -> sdf, grad, inv_s; plus the eikonal term ------------------------------
     float ds_acc = 0.f;
     for (int i = lane; i < S; i += 64) {
-        const float zi = zr[i];
-        const float dist = (i + 1 < S) ? zr[i + 1] - zi : sdist;
-        const float mid = zi + dist * 0.5f;
-        const float px = ox + dx * mid, py = oy + dy * mid, pz = oz + dz * mid;
-        const float pn = sqrtf(px * px + py * py + pz * pz);
-        const float relax = pn < 1.2f ? 1.f : 0.f;
+        const Section sec = section_of(zr, i, S, sdist);
+        const float dist = sec.dist;
+        const float relax = ray_radius(y, sec.mid) < 1.2f ? 1.f : 0.f;
         const size_t q = (size_t)r * S + i;
         const float gx = A.grad[q * 3], gy = A.grad[q * 3 + 1], gz = A.grad[q * 3 + 2];
-        const float tc = dx * gx + dy * gy + dz * gz;
-        const float ic = iter_cos_of(tc, c);
-        const float sd = A.sdf[q];
-        const float ep = sd - ic * dist * 0.5f, en = sd + ic * dist * 0.5f;
-        const float pc = sigmoid_acc(ep * inv_s), nc = sigmoid_acc(en * inv_s);
-        const float raw = (pc - nc + 1e-5f) / (pc + 1e-5f);
-        const float draw = (raw >= 0.f && raw <= 1.f) ? dal0[i] : 0.f;
+        const float tc = y.dx * gx + y.dy * gy + y.dz * gz;
+        const NeusAlpha na = neus_alpha(A.sdf[q], iter_cos_of(tc, c), dist, inv_s);
+        const float ep = na.ep, en = na.en, pc = na.pc, nc = na.nc;
+        const float draw = (na.raw >= 0.f && na.raw <= 1.f) ? dal0[i] : 0.f;
         const float dpc = draw * (nc / ((pc + 1e-5f) * (pc + 1e-5f)));
         const float dnc = -draw / (pc + 1e-5f);
         const float dep_ = dpc * pc * (1.0f - pc), den_ = dnc * nc * (1.0f - nc);  // d/d(arg of sigmoid)
@@ -622,39 +602,25 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(CompArgs A, CompBwd 
         const float gn = sqrtf(gx * gx + gy * gy + gz * gz);
         const float ek = (gn > 0.f) ? deik * relax * 2.0f * (gn - 1.0f) / gn : 0.f;
         G.d_sdf[q] = dep + dne;
-        G.d_grad[q * 3] = dtc * dx + ek * gx;
-        G.d_grad[q * 3 + 1] = dtc * dy + ek * gy;
-        G.d_grad[q * 3 + 2] = dtc * dz + ek * gz;
+        G.d_grad[q * 3] = dtc * y.dx + ek * gx;
+        G.d_grad[q * 3 + 1] = dtc * y.dy + ek * gy;
+        G.d_grad[q * 3 + 2] = dtc * y.dz + ek * gz;
     }
     ds_acc = wave_sum(ds_acc);
     if (lane == 0) G.d_inv_s[r] = ds_acc;  // per-ray term; the caller sums them (no atomics: reproducible)
 }
 
-}  // namespace NCW_RAYNS
-using namespace NCW_RAYNS;
-
 // ------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------
-#ifndef NCW_RAYS_BIG
-extern "C" int ncw_sample_coarse_big(const float*, const float*, const float*, const float*, int, int, int, const float*, const float*,
-                                     float*, float*, float*, void*);
-extern "C" int ncw_upsample_big(const float*, const float*, const float*, const float*, int, int, float, int, float*, void*);
-extern "C" int ncw_sort_merge_big(const float*, int, const float*, int, const float*, const float*, int, float*, float*, void*);
-extern "C" int ncw_composite_fwd_big(const NcwCompositeIn*, const NcwCompositeOut*, void*);
-extern "C" int ncw_composite_bwd_big(const NcwCompositeIn*, const NcwCompositeGrad*, void*);
-#define NCW_RAYS_FORWARD_BIG(cond, call) do { if (cond) return call; } while (0)
-#else
-#define NCW_RAYS_FORWARD_BIG(cond, call) do { } while (0)
-#endif
+// the capacity to instantiate for a ray that needs `slots` LDS slots: 512, else 1088, else 0 (no kernel takes it)
+static int ray_capacity(int slots) { return slots <= RAY_CAP_SMALL ? RAY_CAP_SMALL : slots <= RAY_CAP_LARGE ? RAY_CAP_LARGE : 0; }
 
-extern "C" int NCW_RAYFN(ncw_sample_coarse)(const float* near, const float* far, const float* s_near, const float* s_far, int R,
+extern "C" int ncw_sample_coarse(const float* near, const float* far, const float* s_near, const float* s_far, int R,
                                  int n_samples, int n_outside, const float* rand_shift, const float* rand_out,
                                  float* z, float* z_out, float* sample_dist, void* stream) {
     if (R <= 0) return 0;
-    NCW_RAYS_FORWARD_BIG(n_samples > RAY_MAXN && n_samples <= RAY_MAXN_BIG,
-                         ncw_sample_coarse_big(near, far, s_near, s_far, R, n_samples, n_outside, rand_shift, rand_out, z, z_out, sample_dist, stream));
-    if (n_samples < 1 || n_samples > RAY_MAXN) return NCW_E_BADARG;
+    if (n_samples < 1 || n_samples > RAY_CAP_LARGE) return NCW_E_BADARG;
     dim3 blk(64, 4);
     hipLaunchKernelGGL(sample_coarse_kernel, dim3((R + 3) / 4), blk, 0, (hipStream_t)stream, near, far, s_near, s_far, R,
                        n_samples, n_outside, rand_shift, rand_out, z, z_out, sample_dist);
@@ -662,29 +628,28 @@ extern "C" int NCW_RAYFN(ncw_sample_coarse)(const float* near, const float* far,
     return 0;
 }
 
-extern "C" int NCW_RAYFN(ncw_upsample)(const float* rays_o, const float* rays_d, const float* z, const float* sdf, int R, int n,
+extern "C" int ncw_upsample(const float* rays_o, const float* rays_d, const float* z, const float* sdf, int R, int n,
                             float inv_s, int n_new, float* z_new, void* stream) {
     if (R <= 0 || n_new <= 0) return 0;
-    NCW_RAYS_FORWARD_BIG(n > RAY_MAXN - 1 && n <= RAY_MAXN_BIG - 1, ncw_upsample_big(rays_o, rays_d, z, sdf, R, n, inv_s, n_new, z_new, stream));
-    if (n < 2 || n > RAY_MAXN - 1) return NCW_E_BADARG;
-    hipLaunchKernelGGL(upsample_kernel, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, rays_o, rays_d, z, sdf, R,
-                       n, inv_s, n_new, z_new);
+    const int cap = ray_capacity(n + 1);  // n samples and one more slot for the CDF scan
+    if (n < 2 || !cap) return NCW_E_BADARG;
+    hipLaunchKernelGGL(cap == RAY_CAP_SMALL ? upsample_kernel<RAY_CAP_SMALL> : upsample_kernel<RAY_CAP_LARGE>, dim3((R + 3) / 4),
+                       dim3(256), 0, (hipStream_t)stream, rays_o, rays_d, z, sdf, R, n, inv_s, n_new, z_new);
     NCW_CHECK_LAUNCH();
     return 0;
 }
 
-extern "C" int NCW_RAYFN(ncw_sort_merge)(const float* a, int na, const float* b, int nb, const float* pa, const float* pb, int R,
+extern "C" int ncw_sort_merge(const float* a, int na, const float* b, int nb, const float* pa, const float* pb, int R,
                               float* out, float* pout, void* stream) {
     if (R <= 0 || na + nb <= 0) return 0;
-    NCW_RAYS_FORWARD_BIG(na + nb > RAY_MAXN && na + nb <= RAY_MAXN_BIG, ncw_sort_merge_big(a, na, b, nb, pa, pb, R, out, pout, stream));
-    if (na + nb > RAY_MAXN) return NCW_E_BADARG;
-    hipLaunchKernelGGL(sort_merge_kernel, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, a, na, b, nb, pa, pb, R,
-                       out, pout);
+    const int cap = ray_capacity(na + nb);
+    if (!cap) return NCW_E_BADARG;
+    hipLaunchKernelGGL(cap == RAY_CAP_SMALL ? sort_merge_kernel<RAY_CAP_SMALL> : sort_merge_kernel<RAY_CAP_LARGE>, dim3((R + 3) / 4),
+                       dim3(256), 0, (hipStream_t)stream, a, na, b, nb, pa, pb, R, out, pout);
     NCW_CHECK_LAUNCH();
     return 0;
 }
 
-#ifndef NCW_RAYS_BIG
 extern "C" int ncw_boundary(const float* near, const float* far, const float* z, int n, int R, int nb, float* zb,
                             void* stream) {
     if (R <= 0 || nb <= 0) return 0;
@@ -693,51 +658,32 @@ extern "C" int ncw_boundary(const float* near, const float* far, const float* z,
     NCW_CHECK_LAUNCH();
     return 0;
 }
-#endif
 
-extern "C" int NCW_RAYFN(ncw_composite_fwd)(const NcwCompositeIn* in, const NcwCompositeOut* out, void* stream) {
+extern "C" int ncw_composite_fwd(const NcwCompositeIn* in, const NcwCompositeOut* out, void* stream) {
     if (!in || !out) return NCW_E_BADARG;
     if (in->R <= 0) return 0;
     const int M = in->has_bg ? in->S + in->O : in->S;
-    NCW_RAYS_FORWARD_BIG(M > RAY_MAXN && M <= RAY_MAXN_BIG, ncw_composite_fwd_big(in, out, stream));
-    if (in->S < 1 || M > RAY_MAXN) return NCW_E_BADARG;
-    CompArgs A;
-    A.rays_o = in->rays_o; A.rays_d = in->rays_d; A.z = in->z; A.z_feed = in->z_feed; A.sample_dist = in->sample_dist;
-    A.sdf = in->sdf; A.grad = in->grad; A.rgb = in->rgb; A.density = in->density; A.bg_rgb = in->bg_rgb;
-    A.inv_s = in->inv_s; A.background_rgb = in->background_rgb; A.cos_anneal = in->cos_anneal; A.cos_anneal_dev = in->cos_anneal_dev;
-    A.R = in->R; A.S = in->S; A.O = in->O; A.has_bg = in->has_bg; A.trim_sphere = in->trim_sphere;
-    CompOut Q;
-    Q.color = out->color; Q.color_sphere = out->color_sphere; Q.color_bg = out->color_bg; Q.weights = out->weights;
-    Q.weights_sum = out->weights_sum; Q.cdf = out->cdf; Q.inside = out->inside; Q.depth = out->depth;
-    Q.normals = out->normals; Q.eik = out->eik; Q.mid_z = out->mid_z; Q.dists = out->dists; Q.bg_alpha = out->bg_alpha; Q.weights_max = out->weights_max;
-    hipLaunchKernelGGL(composite_fwd_kernel, dim3((in->R + 3) / 4), dim3(256), 0, (hipStream_t)stream, A, Q);
+    const int cap = ray_capacity(M);
+    if (in->S < 1 || !cap) return NCW_E_BADARG;
+    hipLaunchKernelGGL(cap == RAY_CAP_SMALL ? composite_fwd_kernel<RAY_CAP_SMALL> : composite_fwd_kernel<RAY_CAP_LARGE>, dim3((in->R + 3) / 4), dim3(256), 0, (hipStream_t)stream, *in, *out);
     NCW_CHECK_LAUNCH();
     return 0;
 }
 
-extern "C" int NCW_RAYFN(ncw_composite_bwd)(const NcwCompositeIn* in, const NcwCompositeGrad* g, void* stream) {
+extern "C" int ncw_composite_bwd(const NcwCompositeIn* in, const NcwCompositeGrad* g, void* stream) {
     if (!in || !g) return NCW_E_BADARG;
     if (in->R <= 0) return 0;
     const int M = in->has_bg ? in->S + in->O : in->S;
-    NCW_RAYS_FORWARD_BIG(M > RAY_MAXN && M <= RAY_MAXN_BIG, ncw_composite_bwd_big(in, g, stream));
-    if (in->S < 1 || M > RAY_MAXN) return NCW_E_BADARG;
-    CompArgs A;
-    A.rays_o = in->rays_o; A.rays_d = in->rays_d; A.z = in->z; A.z_feed = in->z_feed; A.sample_dist = in->sample_dist;
-    A.sdf = in->sdf; A.grad = in->grad; A.rgb = in->rgb; A.density = in->density; A.bg_rgb = in->bg_rgb;
-    A.inv_s = in->inv_s; A.background_rgb = in->background_rgb; A.cos_anneal = in->cos_anneal; A.cos_anneal_dev = in->cos_anneal_dev;
-    A.R = in->R; A.S = in->S; A.O = in->O; A.has_bg = in->has_bg; A.trim_sphere = in->trim_sphere;
-    CompBwd G;
-    G.d_color = g->d_color; G.d_wsum = g->d_weights_sum; G.d_depth = g->d_depth; G.d_eik = g->d_eik_num;
-    G.d_sdf = g->d_sdf; G.d_grad = g->d_grad; G.d_rgb = g->d_rgb; G.d_density = g->d_density; G.d_bg_rgb = g->d_bg_rgb;
-    G.d_inv_s = g->d_inv_s;
-    G.grad_scale = g->grad_scale != 0.f ? g->grad_scale : 1.0f;
-    G.grad_scale_dev = g->grad_scale_dev;
-    hipLaunchKernelGGL(composite_bwd_kernel, dim3((in->R + 3) / 4), dim3(256), 0, (hipStream_t)stream, A, G);
+    const int cap = ray_capacity(M);
+    if (in->S < 1 || !cap) return NCW_E_BADARG;
+    NcwCompositeGrad G = *g;
+    if (G.grad_scale == 0.f) G.grad_scale = 1.0f;
+    hipLaunchKernelGGL(cap == RAY_CAP_SMALL ? composite_bwd_kernel<RAY_CAP_SMALL> : composite_bwd_kernel<RAY_CAP_LARGE>, dim3((in->R + 3) / 4), dim3(256), 0, (hipStream_t)stream, *in, G);
     NCW_CHECK_LAUNCH();
     return 0;
 }
 
-#ifndef NCW_RAYS_BIG  // ---- everything below does not keep a ray in LDS: the standard object only --------------------------------------
+// ---- everything below does not keep a ray in LDS --------------------------------------------------------------------------------
 // out[r][j] (+)= sum_i rows[r * per_ray + i][j], i ascending: the order-fixed reduction of the per-point appearance-code
 // adjoints (ncw_color_bwd / ncw_nerf_bwd with d_a_rows) to the per-ray gradient of the embedding lookup
 // (models/neuconw.py:131-139, nerf.py:159-160: `a` is repeated over a ray's samples, so autograd sums over them).
@@ -989,18 +935,12 @@ struct BgSel {
     int R, S, O;
 };
 
-// keep flag of sample i of ray r: the n_outside samples always; a primary sample iff the compositor's own inside_sphere
-// (composite_fwd_kernel: section mid-point of the PRIMARY z, the last section ends sample_dist further) is 0
-NCW_DEV bool bg_keep(const BgSel& A, int r, int i, const float (&o)[3], const float (&d)[3]) {
-    const int M = A.S + A.O;
-    if (i >= A.S) return i < M;
-    // A.z = the PRIMARY z [R, S]: the compositor pairs column i < S of the background arrays with primary sample i by
-    // INDEX (background_alpha[:, :n_samples] * (1 - inside_sphere), renderer.py:693), wherever z_feed's i-th point lies
-    const float zi = A.z[(size_t)r * A.S + i];
-    const float dist = (i + 1 < A.S) ? A.z[(size_t)r * A.S + i + 1] - zi : A.sample_dist[r];
-    const float zz = zi + dist * 0.5f;
-    const float x = o[0] + d[0] * zz, y = o[1] + d[1] * zz, w = o[2] + d[2] * zz;
-    return !(sqrtf(x * x + y * y + w * w) < 1.0f);  // inside_sphere = (|p| < 1): renderer.py:637
+// keep flag of sample i of a ray: the n_outside samples always; a primary sample iff the compositor's inside_sphere of section i
+// of the PRIMARY z [R, S] is 0 -- the compositor pairs column i < S of the background arrays with primary sample i by INDEX
+// (background_alpha[:, :n_samples] * (1 - inside_sphere), renderer.py:693), wherever z_feed's i-th point lies
+NCW_DEV bool bg_keep(const BgSel& A, int r, int i, const Ray& y, float sdist) {
+    if (i >= A.S) return i < A.S + A.O;
+    return !section_inside(y, A.z + (size_t)r * A.S, i, A.S, sdist);
 }
 
 template <bool WRITE>
@@ -1009,12 +949,12 @@ __global__ __launch_bounds__(256) void bg_select_ray_kernel(BgSel A, int32_t* __
     if (r >= A.R) return;  // wave-uniform
     const int lane = threadIdx.x & 63;
     const int M = A.S + A.O;
-    const float o[3] = {A.rays_o[r * 3], A.rays_o[r * 3 + 1], A.rays_o[r * 3 + 2]};
-    const float d[3] = {A.rays_d[r * 3], A.rays_d[r * 3 + 1], A.rays_d[r * 3 + 2]};
+    const Ray y = load_ray(A.rays_o, A.rays_d, r);
+    const float sdist = A.sample_dist[r];
     int at = WRITE ? offs[r] : 0;
     for (int i0 = 0; i0 < M; i0 += 64) {
         const int i = i0 + lane;
-        const bool keep = i < M && bg_keep(A, r, i, o, d);
+        const bool keep = i < M && bg_keep(A, r, i, y, sdist);
         const unsigned long long m = __ballot(keep);
         if (WRITE && keep) idx[at + __popcll(m & ((1ull << lane) - 1ull))] = r * M + i;
         at += __popcll(m);
@@ -1075,4 +1015,3 @@ extern "C" int ncw_bg_select(const float* rays_o, const float* rays_d, const flo
     }
     return 0;
 }
-#endif  // !NCW_RAYS_BIG

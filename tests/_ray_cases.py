@@ -83,7 +83,7 @@ _SEEDS = {(1088, 0, 5): 1096}
 
 SHAPES_STD = [(1, 0), (1, 1), (2, 0), (63, 0), (64, 0), (65, 0), (60, 4), (61, 4), (127, 2), (448, 64), (512, 0)]
 SHAPES_BIG = [(509, 4), (512, 1), (1024, 32), (1056, 32), (1088, 0)]
-OPTION_SHAPES = [(61, 4), (509, 4)]  # one per object
+OPTION_SHAPES = [(61, 4), (509, 4)]  # one per capacity
 INDEP_SHAPES = [(61, 4), (1056, 32)]
 
 
@@ -247,7 +247,7 @@ def slice_rays(I, r0, r1):
 # upsample
 # --------------------------------------------------------------------------------------------------------------------
 UPSAMPLE_R = 41
-# (n, n_new, inv_s); n >= 512 runs on the large-ray object
+# (n, n_new, inv_s); n >= 512 runs on the large-ray instantiation
 UPSAMPLE_SHAPES = [(3, 5, 64.0), (511, 128, 512.0), (2, 1, 512.0), (2, 8, 512.0), (64, 65, 512.0), (65, 64, 1024.0),
                    (129, 128, 2048.0), (512, 128, 1024.0), (1087, 128, 4096.0), (1024, 1, 512.0)]
 UPSAMPLE_INDEP = [(65, 64, 1024.0), (1087, 128, 4096.0)]

@@ -1,5 +1,5 @@
 """Edge cases of the hot path through the C ABI: empty inputs, a single ray, the maximum samples-per-ray the
-per-ray kernels hold in LDS (S + O = 512 in the standard object, 1088 in the large-ray one) and past it (must fail loudly), bad arguments."""
+per-ray kernels hold in LDS (S + O = 512 in the standard instantiation, 1088 in the large-ray one) and past it (must fail loudly), bad arguments."""
 import pytest
 import torch
 
@@ -43,8 +43,8 @@ def test_single_ray_matches_oracle():
 
 
 def test_max_samples_per_ray_and_one_past():
-    """S + O = 512 is the STANDARD per-ray kernels' LDS capacity (RAY_MAXN): it must work and match the oracle; more goes to the
-    large-ray object (test_more_than_512_samples_per_ray); beyond 1088 must raise instead of truncating."""
+    """S + O = 512 is the STANDARD per-ray kernels' LDS capacity (RAY_CAP_SMALL): it must work and match the oracle; more goes to the
+    large-ray instantiation (test_more_than_512_samples_per_ray); beyond 1088 must raise instead of truncating."""
     import neuralrecon_w_amd as nw
     from oracle import neuconw_oracle as O
 
@@ -63,7 +63,7 @@ def test_max_samples_per_ray_and_one_past():
     assert max(errs.values()) < 1e-4, errs
     with pytest.raises(ValueError, match="1088"):  # beyond the large-ray kernels' capacity: refused at construction, with the reason
         build_system(seed=3, prec=nw.PREC_F32, n_samples=544, n_importance=544)
-    # ... and the C ABI itself refuses an over-long ray instead of truncating it (600 samples: the large-ray object takes it)
+    # ... and the C ABI itself refuses an over-long ray instead of truncating it (600 samples: the large-ray instantiation takes it)
     from neuralrecon_w_amd import rayops
     a, b = torch.rand(4, 300, device="cuda"), torch.rand(4, 300, device="cuda")
     merged, _ = rayops.sort_merge(a, b)
@@ -88,7 +88,7 @@ def test_bad_arguments_fail_loudly():
 @pytest.mark.parametrize("ns,ni,n_out,steps", [(256, 256, 32, 4), (512, 512, 32, 4)])
 def test_more_than_512_samples_per_ray(ns, ni, n_out, steps):
     """config/defaults.py:8-9,31-32 (N_SAMPLES = N_IMPORTANCE = 512, UP_SAMPLE_STEP 4, N_OUTSIDE 32): 1056 samples per ray.  The per-ray
-    kernels' large-ray object (csrc/ncw_rays.hip, -DNCW_RAYS_BIG: 1088 samples in LDS) takes over above 512; render + loss + backward
+    kernels' large-ray instantiation (csrc/ncw_rays.hip, RAY_CAP_LARGE: 1088 samples in LDS) takes over above 512; render + loss + backward
     against the fp32 oracle on a few rays."""
     import neuralrecon_w_amd as nw
     from oracle import neuconw_oracle as O

@@ -1,5 +1,5 @@
-"""The per-ray sampler and compositor kernels (csrc/ncw_rays.hip, both objects: the standard one up to 512 samples per ray, the
-large-ray one -DNCW_RAYS_BIG up to 1088) called directly at their shape edges and down the branches no render reaches.
+"""The per-ray sampler and compositor kernels (csrc/ncw_rays.hip, both capacities of its LDS kernels: the instantiation for up to 512
+samples per ray -- "standard" below -- and the "large-ray" one up to 1088) called directly at their shape edges and down the branches no render reaches.
 
 References, cases and the bound are in tests/_ray_cases.py: oracle/neuconw_oracle.py in float64 arbitrates; the same in float32
 on the CPU is the "fp32 restatement"; every comparison asserts err_kernel <= max(floor, 4 * err_fp32_restatement), both errors
@@ -18,7 +18,7 @@ well inside the factor 4; the worst ratio to its bound anywhere is 0.30):
   sample_coarse   standard   1.8e-07 / 1.8e-07 (n = 1)          large-ray  1.5e-07 / 1.5e-07 (n = 513)
   boundary                   6.1e-08 / 7.0e-08 (n = 24, nb = 65)
   upsample        standard   2.6e-06 / 2.6e-06 at (3, 5, 64)    large-ray  5.1e-06 / 1.8e-05 at (512, 128, 1024)
-  sort_merge                 exact, both objects
+  sort_merge                 exact, both capacities
 """
 import pytest
 import torch
@@ -86,7 +86,7 @@ def _compare(c, fwd, adj):
 def test_composite_shapes(c):
     """One launch scans three lengths (S for depth and the sphere colour, M = S + O for the merged and background chains) with
     per = ceil(m / 64) elements per lane: m below 64, on and next to multiples of 64, S and M on opposite sides of one, the
-    capacity of each object (512 / 1088) and the first size of the large-ray object (513).  Pins wave_excl_scan /
+    capacity of each instantiation (512 / 1088) and the first size of the large-ray one (513).  Pins wave_excl_scan /
     wave_suffix_excl_sum at every `per`, weights_max over all M columns and bg_alpha."""
     _compare(c, *_run_comp(C.comp_case_inputs(c), c))
 
@@ -197,7 +197,7 @@ def _check_coarse(K, n, no, tag):
 def test_sample_coarse_shapes(n):
     """sample_coarse_kernel's stride loops (64 lanes per ray): n_samples and n_outside below, at and past one trip, steps == 1 of
     torch_linspace (n = 1, n_outside = 1), no outside samples, the perturbed branch with its neighbour look-ups at both ends, R = 1
-    and R = 5 (a second, partly filled workgroup); n > 512 runs in the large-ray object."""
+    and R = 5 (a second, partly filled workgroup); n up to 1088 is accepted (the kernel keeps no ray in LDS)."""
     worst = (0.0, 0.0)
     for no in C.COARSE_OUT:
         for perturb in (False, True):
@@ -219,7 +219,7 @@ def test_sample_coarse_window(n):
 def test_boundary_vs_oracle(n, nb):
     """boundary_kernel: nb // 2 samples in [near, z_first), the rest in (z_last, far]; nb = 1 has no near part, nb > 64 takes a
     second trip of the stride loop.  Then the merge the renderer does with them: sort_merge(zb, z) equals the sorted
-    concatenation of the kernel's own two operands exactly (n = 600 with nb = 130: 730 elements, the large-ray object)."""
+    concatenation of the kernel's own two operands exactly (n = 600 with nb = 130: 730 elements, the large-ray instantiation)."""
     from neuralrecon_w_amd import rayops
 
     B = C.boundary_case(n, nb)
@@ -238,8 +238,8 @@ def test_boundary_vs_oracle(n, nb):
 @pytest.mark.parametrize("n,n_new,inv_s", C.UPSAMPLE_SHAPES)
 def test_upsample_shapes(n, n_new, inv_s):
     """upsample_kernel: m = n - 1 sections and the m + 1 = n slot CDF scan on both sides of multiples of 64, the smallest ray
-    (n = 2), n_new = 1 (steps == 1 of torch_linspace) and n_new past one trip; 511 is the standard object's capacity, 512 the
-    large-ray object's first size, 1087 its capacity.  Per ray against float64; a ray is left out exactly where the fp32
+    (n = 2), n_new = 1 (steps == 1 of torch_linspace) and n_new past one trip; 511 is the standard instantiation's capacity, 512 the
+    large-ray one's first size, 1087 its capacity.  Per ray against float64; a ray is left out exactly where the fp32
     restatement itself is off (sample_pdf's denominator switch at 1e-5, decided in tests/_ray_cases.py); sortedness holds on all."""
     from neuralrecon_w_amd import rayops
 
@@ -256,7 +256,7 @@ def test_upsample_shapes(n, n_new, inv_s):
 @pytest.mark.parametrize("n,n_new,inv_s", C.UPSAMPLE_INDEP)
 def test_upsample_rays_independent_and_repeatable(n, n_new, inv_s):
     """upsample_kernel keeps four rays per workgroup in LDS rows sm[wv]: a ray run alone (R = 1) gives bit for bit what it gives
-    among nine (three workgroups, the last with one ray: the `r >= R` exit), and a second run equals the first; both objects."""
+    among nine (three workgroups, the last with one ray: the `r >= R` exit), and a second run equals the first; both capacities."""
     from neuralrecon_w_amd import rayops
 
     U = C.upsample_case(n, n_new, inv_s)
@@ -287,7 +287,7 @@ def test_sort_merge_shapes(na, nb):
 
 @pytest.mark.parametrize("na,nb", C.MERGE_INDEP)
 def test_sort_merge_rays_independent_and_repeatable(na, nb):
-    """sort_merge_kernel, the same: one LDS row per wave, nine rays against each alone, and a repeated run; both objects."""
+    """sort_merge_kernel, the same: one LDS row per wave, nine rays against each alone, and a repeated run; both capacities."""
     from neuralrecon_w_amd import rayops
 
     M = C.merge_case(na, nb, R=9)
@@ -301,8 +301,8 @@ def test_sort_merge_rays_independent_and_repeatable(na, nb):
 
 
 # --------------------------------------------------------------------------------------------------------------------
-# argument checks: each of these returns NCW_E_BADARG in csrc/ncw_rays.hip before any launch (the size is neither taken by the
-# standard object nor forwarded to the large-ray one), so no kernel ever sees an over-long ray
+# argument checks: each of these returns NCW_E_BADARG in csrc/ncw_rays.hip before any launch (the size fits neither
+# capacity), so no kernel ever sees an over-long ray
 # --------------------------------------------------------------------------------------------------------------------
 def test_bad_sizes_raise():
     import neuralrecon_w_amd as nw
@@ -310,20 +310,20 @@ def test_bad_sizes_raise():
 
     dev = "cuda"
     o = torch.zeros(2, 3, device=dev)
-    for n in (1, 1088):  # ncw_upsample: n < 2, n > RAY_MAXN_BIG - 1
+    for n in (1, 1088):  # ncw_upsample: n < 2, n > 1088 - 1
         with pytest.raises(nw.NeuconwHipError):
             rayops.upsample(o, o, torch.zeros(2, n, device=dev), torch.zeros(2, n, device=dev), 4, 64.0)
     near, far = torch.ones(2, 1, device=dev), torch.full((2, 1), 3.0, device=dev)
-    for n in (0, 1089):  # ncw_sample_coarse: n_samples < 1, > RAY_MAXN_BIG
+    for n in (0, 1089):  # ncw_sample_coarse: n_samples < 1, > 1088
         with pytest.raises(nw.NeuconwHipError):
             rayops.sample_coarse(near, far, near, far, n, 4)
-    with pytest.raises(nw.NeuconwHipError):  # ncw_sort_merge: na + nb > RAY_MAXN_BIG
+    with pytest.raises(nw.NeuconwHipError):  # ncw_sort_merge: na + nb > 1088
         rayops.sort_merge(torch.zeros(2, 1000, device=dev), torch.zeros(2, 89, device=dev))
     e = lambda *s: torch.zeros(*s, device=dev)  # noqa: E731
     long_ray = {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in C.comp_inputs(2, 1057, 32, 3).items()}
     no_sample = dict(o=o, d=o, z=e(2, 0), sample_dist=e(2, 1), sdf=e(2, 0), grad=e(2, 0, 3), rgb=e(2, 0, 3), inv_s=e(1) + 20,
                      z_feed=None, density=None, bg_rgb=None)
-    for I in (long_ray, no_sample):  # ncw_composite_fwd / _bwd: M = 1089 > RAY_MAXN_BIG, S = 0 < 1
+    for I in (long_ray, no_sample):  # ncw_composite_fwd / _bwd: M = 1089 > 1088, S = 0 < 1
         ctx = rayops.CompositeCtx(I["o"], I["d"], I["z"], I["sample_dist"], I["sdf"], I["grad"], I["rgb"], I["inv_s"], 0.3,
                                   I["z_feed"], I["density"], I["bg_rgb"])
         with pytest.raises(nw.NeuconwHipError):
