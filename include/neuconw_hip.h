@@ -857,6 +857,31 @@ int ncw_surf_pick(const double* cdf, int64_t n_faces, const double* x, int64_t n
 int ncw_surf_sample(const double* verts, const int32_t* faces, const double* cdf, int64_t n_faces, uint64_t seed, int64_t i0,
                     int64_t n, int64_t n_total, int mode, double* pts, int32_t* tri, double* urr, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * View selection (csrc/ncw_roi.hip): the region-of-interest test of the split writer, for ALL registered views of a scene in
+ * one launch.  The reference runs it per image (tools/prepare_data/dataset_filter_utils.py:160-178: get_ray_directions +
+ * get_rays + eight torch ops, after a full decode of the image that is only used for its size); it needs no per-pixel input.
+ *   ncw_views_roi : cams_dev [n_views] (DEVICE table; near / far are not read), pix_start_dev [n_views + 1] int64 (DEVICE): the
+ *                   exclusive prefix sum of width * height, so that pixel (row, col) of view v is global pixel
+ *                   pix_start[v] + row * width + col.  Ray of the pixel: ncw_view_rays' arithmetic (integer pixel
+ *                   coordinates, o = c2w[:, 3], d normalised).  In float32, in the reference's order of operations (:171-177),
+ *                   with origin_host[3] and radius the scene sphere of config.yaml:
+ *                       c = origin - o;  dot = sum(c * d);  p = dot * d;  dist_ray = |c - p|;  dist_cam = |c|
+ *                       roi = (radius > dist_cam  or  dot > 0)  and  dist_ray < radius
+ *                   count_dev [n_views] uint32 = number of roi pixels of each view (:178 is count / (w h)); the entry point
+ *                   clears it on `stream`.  Per wave the 64-bit ballot and its population count, across the waves integer
+ *                   adds in LDS, then one integer atomicAdd per workgroup and view it touches (a workgroup's run of pixels
+ *                   may straddle views; past eight views per run the adds are per wave): no float atomics, the counts are
+ *                   bitwise reproducible.  mask_dev: NULL, or
+ *                   [pix_start[n_views]] uint8 that receives 0 / 1 per pixel.  ONE launch of a fixed grid whatever the scene;
+ *                   the workgroup -> (view, tile) mapping is a binary search of pix_start_dev on the device.  The entry point
+ *                   allocates nothing, reads nothing back and does no per-view host work; the kernel reads the camera table
+ *                   and pix_start and nothing else.
+ * Returns NCW_E_BADARG without a launch for NULL cams / pix_start / origin / count, n_views < 1 or radius <= 0 (or NaN).
+ * ---------------------------------------------------------------------------------------- */
+int ncw_views_roi(const NcwViewCamera* cams_dev, const int64_t* pix_start_dev, int n_views, const float* origin_host, float radius,
+                  uint32_t* count_dev, uint8_t* mask_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
