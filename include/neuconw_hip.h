@@ -882,6 +882,57 @@ int ncw_surf_sample(const double* verts, const int32_t* faces, const double* cdf
 int ncw_views_roi(const NcwViewCamera* cams_dev, const int64_t* pix_start_dev, int n_views, const float* origin_host, float radius,
                   uint32_t* count_dev, uint8_t* mask_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Checking the alignment (csrc/ncw_gtreproj.hip): the ground-truth reprojection error of SfM tracks, tools/reproj_error.py --
+ * the one check of the sfm2gt matrix that the evaluation chain multiplies by.
+ *   ncw_pixel_nearest : replaces reproj_error.py:21-51 (get_gt_point), for ALL queries in one pass over the cloud.  For each of
+ *                       the n_queries queries of queries_dev (DEVICE table) it finds, among the n points xyz_dev [n,3] f32 (the
+ *                       points p0 .. p0 + n - 1 of the cloud), the one nearest to the camera that projects onto the query's
+ *                       pixel.  Float32, no contraction, every product and sum rounded in the order written:
+ *                           X = rintf(qx);  Y = rintf(qy)                              (torch.round: ties to even)
+ *                           c_k = ((w_k0 x + w_k1 y) + w_k2 z) + w_k3                  (k = 0, 1, 2; w = w2c row-major)
+ *                           u = (fx c_0 + cx c_2) / c_2;  v = (fy c_1 + cy c_2) / c_2  (IEEE division)
+ *                           hit = rintf(u) == X  and  rintf(v) == Y  and  c_2 >= 0
+ *                           key = (bits(c_2 + 0.0f) << 32) | (p0 + i)
+ *                           best[q] = min(best[q], key)                                (64-bit integer atomicMin)
+ *                       c_2 >= 0: the bit pattern orders like the value, so the minimum is the nearest point and equal depths
+ *                       resolve to the lowest index.  clear != 0 first fills best_dev [n_queries] uint64 with all-ones on
+ *                       `stream`; a query that no point hits keeps all-ones.  The integer minimum does not depend on arrival
+ *                       order: the result is bitwise reproducible and bitwise the same for any split of the cloud into launches
+ *                       (p0, clear = 0).  No float atomics.  A workgroup owns NCW_PIXNN_WG_POINTS consecutive points in registers
+ *                       and walks the queries in LDS tiles of NCW_PIXNN_QUERY_TILE; a division-free bound that is a superset of
+ *                       the predicate (argued in the source) keeps the divisions to about one pair in width x height.
+ *                       Returns NCW_E_BADARG without a launch for a NULL pointer, n_queries < 1, n < 0, p0 < 0 or
+ *                       p0 + n > 2^32 - 1; n == 0 with clear set only clears.
+ *   ncw_reproj_errors : replaces reproj_error.py:120-138 (image_reproj_error) and :233-236 (the per-track-element errors):
+ *                       err[i] = |(P [p, 1])_xy / (P [p, 1])_z - xy[i]| with P = proj_dev[cam_idx[i]] (3x4 row-major, K [R|t]),
+ *                       p = xyz_dev[pt_idx[i]], in float32 without contraction:
+ *                           h_k = ((P_k0 x + P_k1 y) + P_k2 z) + P_k3;  dx = h_0 / h_2 - xy[i][0];  dy = h_1 / h_2 - xy[i][1]
+ *                           err[i] = sqrtf(dx dx + dy dy)
+ *                       and seg_sum[s] (float64) = the sum of err over the observations seg_start[s] .. seg_start[s + 1] - 1
+ *                       (seg_start_dev [n_seg + 1] int64, DEVICE, ascending; clamped to [0, n_obs]).  One wave per segment:
+ *                       lane l adds the observations l, l + 64, .. of the segment in sequence in float64, then a fixed xor
+ *                       butterfly (32, 16, .. 1) sums the lanes: the order is fixed by the segment alone, so seg_sum is bitwise
+ *                       reproducible; an empty segment gives 0.  err is written for the observations inside a segment.  A camera
+ *                       or point index outside [0, n_cams) / [0, n_pts) reads nothing and gives NaN.
+ *                       Returns NCW_E_BADARG without a launch for a NULL pointer, n_cams < 1, n_pts < 1, n_obs < 0 or n_seg < 0;
+ *                       0 without a launch for n_seg == 0.
+ * ---------------------------------------------------------------------------------------- */
+#define NCW_PIXNN_WG_POINTS 2048
+#define NCW_PIXNN_QUERY_TILE 256
+
+typedef struct NcwPixelQuery {
+    float w2c[12];          /* world -> camera, 3x4 row-major */
+    float fx, fy, cx, cy;
+    float qx, qy;           /* the key-point */
+} NcwPixelQuery;
+
+int ncw_pixel_nearest(const NcwPixelQuery* queries_dev, int n_queries, const float* xyz_dev, int64_t p0, int64_t n, int clear,
+                      uint64_t* best_dev, void* stream);
+int ncw_reproj_errors(const float* proj_dev, int n_cams, const float* xyz_dev, int64_t n_pts, const int32_t* cam_idx_dev,
+                      const int32_t* pt_idx_dev, const float* xy_dev, int64_t n_obs, const int64_t* seg_start_dev, int64_t n_seg,
+                      float* err_dev, double* seg_sum_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

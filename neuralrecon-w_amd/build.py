@@ -28,6 +28,9 @@ elif any(f.startswith("-DNCW_EXP_") for f in FLAGS):
 # the defaults).  Nothing in it branches on NaNs.
 MLP_FLAGS = ["-fno-honor-nans", "-mno-amdgpu-ieee", "-fno-slp-vectorize"]
 MLP_FILES = {"ncw_pp.hip"}
+# ncw_gtreproj.hip is a pure VALU loop of separately rounded float32 products and sums.  The SLP vectoriser pairs them ACROSS
+# the u / v halves of one point into v_pk_mul_f32 / v_pk_add_f32 and pays for it with register moves and split LDS reads.
+FILE_FLAGS = {"ncw_gtreproj.hip": ["-fno-slp-vectorize"]}
 if TAG and "NCW_MLP_FLAGS" in os.environ:  # A/B probe builds (scripts/): e.g. NCW_MLP_FLAGS="" NCW_BUILD_TAG=plain
     MLP_FLAGS = os.environ["NCW_MLP_FLAGS"].split()
 # second flag group (A/B probe builds only): NCW_FLAGS2 applied to the files listed in NCW_FILES2
@@ -91,7 +94,7 @@ def _compile(job):
     srcp = os.path.join(CSRC, src)
     if os.path.exists(obj) and os.path.getmtime(obj) > max(os.path.getmtime(srcp), _deps_mtime()):
         return obj, False
-    cmd = [HIPCC] + FLAGS + (MLP_FLAGS if src in MLP_FILES else []) + (FLAGS2 if src in FILES2 else []) + (["-DNCW_HALF_F16"] if f16 else [])
+    cmd = [HIPCC] + FLAGS + (MLP_FLAGS if src in MLP_FILES else []) + FILE_FLAGS.get(src, []) + (FLAGS2 if src in FILES2 else []) + (["-DNCW_HALF_F16"] if f16 else [])
     cmd += ["-c", srcp, "-o", obj]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:

@@ -73,11 +73,13 @@ def read_images(path, with_points=False):
     return imgs
 
 
-def read_points3d(path):
+def read_points3d(path, with_tracks=False):
     """COLMAP points3D.bin (utils/colmap_utils.py:264-291: uint64 count, then per point `<QdddBBBd` + uint64 track length + that
     many `<ii` track elements) -> (ids int64 [N], xyz float64 [N,3], reprojection error float64 [N], track length int64 [N]),
     file order.  The one walk of the file: voxel.read_points3d_xyz, evalmesh.read_points3d_filtered and
-    cachebuild.read_points3d_table are views of what it returns."""
+    cachebuild.read_points3d_table are views of what it returns.  with_tracks: the tuple also carries the track elements as CSR
+    arrays, (.., track_start int64 [N + 1], track_image_id int32 [T], track_point2d_idx int32 [T]): the elements of point i are
+    track_start[i] .. track_start[i + 1] - 1, in file order (gtreproj.select_tracks)."""
     with open(path, "rb") as fh:
         buf = fh.read()
     (n,) = struct.unpack_from("<Q", buf, 0)
@@ -86,14 +88,21 @@ def read_points3d(path):
     xyz = np.empty((n, 3), dtype=np.float64)
     err = np.empty(n, dtype=np.float64)
     track = np.empty(n, dtype=np.int64)
+    elems = []
     for i in range(n):
         ids[i], xyz[i, 0], xyz[i, 1], xyz[i, 2] = struct.unpack_from("<Qddd", buf, off)
         (err[i],) = struct.unpack_from("<d", buf, off + 35)
         (track[i],) = struct.unpack_from("<Q", buf, off + 43)
+        elems.append((off + 51, 2 * int(track[i])))
         off += 51 + 8 * int(track[i])
     if off != len(buf):
         raise ValueError("%s: %d trailing bytes after %d points (not a COLMAP points3D.bin?)" % (path, len(buf) - off, n))
-    return ids, xyz, err, track
+    if not with_tracks:
+        return ids, xyz, err, track
+    flat = np.concatenate([np.frombuffer(buf, dtype="<i4", count=c, offset=o) for o, c in elems] + [np.empty(0, dtype="<i4")])
+    flat = flat.astype(np.int32).reshape(-1, 2)
+    start = np.concatenate([[0], np.cumsum(track)]).astype(np.int64)
+    return ids, xyz, err, track, start, np.ascontiguousarray(flat[:, 0]), np.ascontiguousarray(flat[:, 1])
 
 
 def qvec2rotmat(q):
