@@ -38,6 +38,46 @@ NCW_DEV void sb_load_slice(bf16x8* a, const void* w, int rb_stride, int ob, int 
 }
 
 // ------------------------------------------------------------------------------------------------
+// The MFMA loop of the background kernels (nerf_fwdB / nerf_bwdB): acc0 (+ acc1) += w[u] . B[u] over NU k-units of one or
+// two tiles, the B fragments read from LDS through an explicit register ring SB_RD units ahead of their MFMA and the issue
+// order pinned per unit (ncw_split.hip s2_segment).  Left to the compiler, every ds_read_b128 of the forward was followed
+// by lgkmcnt(0) and its MFMA (NOTEBOOK R7).  in0 / in1 = the tile's first unit + lane, units 1 KiB apart.  The ring is primed
+// here, i.e. after the barrier that published the buffer, and is empty on return: no read is carried across a barrier.
+// NPF > 0: units 0 .. NPF-1 of the NEXT slice (wn, fragment u * rb_stride + ob) replace w[u] once its MFMAs are issued -- the
+// slice is reloaded IN PLACE during the layer's last call, so one slice of registers (64) serves the whole kernel and there
+// is no second slice to copy from.  What a layer needs besides (bias fragment, ReLU masks, per-ray rows) is requested BEFORE
+// that call: the memory pipe returns in order, so its wait is then a counted vmcnt(N) that leaves the slice in flight.
+// The MFMA order per accumulator is the k order, acc0 before acc1: results do not depend on SB_RD.
+// ------------------------------------------------------------------------------------------------
+constexpr int SB_RD = 4;  // one-stream bench, nerf_fwdB / nerf_bwdB: 0.258 / 0.399 ms at 4, 0.261 / 0.397 at 6, 0.268 / 0.400 at 8 (spills)
+
+template <int NU, bool TWO, int NPF = 0>
+NCW_DEV void sb_mma(f32x16& acc0, f32x16& acc1, bf16x8* w, const sb_lfrag* in0, const sb_lfrag* in1, const void* wn = nullptr,
+                    int rb_stride = 0, int ob = 0, int lane = 0) {
+    constexpr int RD = SB_RD < NU ? SB_RD : NU, R = RD + 1 < NU ? RD + 1 : NU;
+    bf16x8 b[R][TWO ? 2 : 1];
+#pragma unroll
+    for (int q = 0; q < RD; ++q) {
+        b[q][0] = in0[q * 64];
+        if (TWO) b[q][TWO ? 1 : 0] = in1[q * 64];
+    }
+#pragma unroll
+    for (int u = 0; u < NU; ++u) {
+        // (the reload of unit u - 1 sits BEHIND the fence that follows its MFMAs: in one scheduling region with them the
+        // compiler hoists the load above the MFMAs, into fresh registers, and spills)
+        if (u >= 1 && u - 1 < NPF) w[u - 1] = ncw_ld_frag<bf16x8>(wn, (size_t)(u - 1) * rb_stride + ob, lane);
+        if (u + RD < NU) {
+            b[(u + RD) % R][0] = in0[(u + RD) * 64];
+            if (TWO) b[(u + RD) % R][TWO ? 1 : 0] = in1[(u + RD) * 64];
+        }
+        acc0 = NCW_MFMA_H(w[u], b[u % R][0], acc0, 0, 0, 0);
+        if (TWO) acc1 = NCW_MFMA_H(w[u], b[u % R][TWO ? 1 : 0], acc1, 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    if (NU - 1 < NPF) w[NU - 1] = ncw_ld_frag<bf16x8>(wn, (size_t)(NU - 1) * rb_stride + ob, lane);
+}
+
+// ------------------------------------------------------------------------------------------------
 // sdf_fwd in the weights-stationary structure: forward chain with the activation stash, feature
 // layer, sdf row, then the analytic adjoint pass a_{l-1} = W_l^T (a_l * phi'(z_l)) with the t_l stash and
 // grad = J_gamma^T g_gamma -- the same arithmetic as sdf_fwd_kernel (ncw_sdf.hip), W = 256 bf16.
@@ -292,7 +332,16 @@ __global__ __launch_bounds__(64 * SB_WAVES) void sdf_fwdB_kernel(NcwSdfNet net, 
 constexpr int SB_X = SB_TILES * 6 * 1024;
 
 NCW_DEV void inverted_sphere8(const float (&x)[3], float (&p4)[4]) {  // renderer.py:181-186
-    float r = sqrtf(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+    // |x|^2 with its roundings WRITTEN DOWN: left to the compiler, which of the three squares is fused into an FMA follows the
+    // vectoriser's pairing and changed with the code around this function -- one ulp in r, which the 2^9 of gamma_10 turns into
+    // other 16-bit features for 0.25 % of the points (NOTEBOOK R7.1).  This is the form every build so far happened to have.
+    float r2;
+    {
+#pragma clang fp contract(off)
+        const float s1 = x[1] * x[1], s2 = x[2] * x[2];
+        r2 = __builtin_fmaf(x[0], x[0], s1) + s2;
+    }
+    float r = sqrtf(r2);
     r = fminf(fmaxf(r, 1.0f), 1e10f);
     p4[0] = x[0] / r; p4[1] = x[1] / r; p4[2] = x[2] / r; p4[3] = 1.0f / r;
 }
@@ -347,7 +396,7 @@ __global__ __launch_bounds__(64 * SB_WAVES) void nerf_fwdB_kernel(NcwNerfNet net
             stash_store<3>((SE*)st.aux1, (size_t)(tile0 + wave), aux1, lane);  // re-read for the head (same bf16 values)
         }
     }
-    bf16x8 wa[16], wb[16], wx[6];
+    bf16x8 wa[16], wx[6];
     auto bias_of = [&](const float* bp, int ob) {
         CVec<1> b1;
         load_bias(b1, bp + ob * 32, lane);
@@ -359,48 +408,42 @@ __global__ __launch_bounds__(64 * SB_WAVES) void nerf_fwdB_kernel(NcwNerfNet net
         for (int r = 0; r < 16; ++r) y[r] = ncw_relu(v[r]);
         return y;
     };
+    f32x16 bnext;  // the NEXT layer's bias fragment: requested one layer ahead, before the slice that is reloaded meanwhile
     // ---- trunk layer 0 (K = 84: the 6 units of gamma(p)) ---------------------------------------------------
     {
         bf16x8 w0[6];
-        sb_load_slice<6>(w0, net.w_p[0], 8, wave, 0, lane);
-        sb_load_slice<16>(wa, D > 1 ? net.w_p[1] : net.w_feat, 8, wave, 0, lane);
         const f32x16 bias = bias_of(net.b_p[0], wave);
+        sb_load_slice<6>(w0, net.w_p[0], 8, wave, 0, lane);
+        bnext = bias_of(D > 1 ? net.b_p[1] : net.b_feat, wave);
+        sb_load_slice<16>(wa, D > 1 ? net.w_p[1] : net.w_feat, 8, wave, 0, lane);
         ncw_lds_barrier();
 #pragma unroll
         for (int t = 0; t < SB_TILES; ++t) {
             f32x16 acc = bias;
-#pragma unroll
-            for (int q = 0; q < 6; ++q) acc = NCW_MFMA_H(w0[q], xbuf[(t * 6 + q) * 64 + lane], acc, 0, 0, 0);
+            sb_mma<6, false>(acc, acc, w0, xbuf + t * 6 * 64 + lane, nullptr);
             const f32x16 y = relu16(acc);
             if (TRAIN) stash_store_block((SE*)st.h[1], (size_t)(tile0 + t), 8, wave, y, lane);
             sb_store_units(abuf0, t, wave, y, lane);
         }
     }
     int cur = 0;
-    // ---- trunk layers 1 .. D-1 -----------------------------------------------------------------------------
+    // ---- trunk layers 1 .. D-1 (wa = slice of w_p[i]; the next layer's -- or w_feat's -- replaces it during the last tile pair) ----
     for (int i = 1; i < D; ++i) {
         const bool skip = (i == net.skip + 1);
+        const void* wnext = i + 1 < D ? net.w_p[i + 1] : net.w_feat;
+        const f32x16 bias = bnext;
         if (skip) sb_load_slice<6>(wx, net.w_p[i], 8, wave, 16, lane);  // units 16..21 = the gamma(p) columns
-        sb_load_slice<16>(wb, i + 1 < D ? net.w_p[i + 1] : net.w_feat, 8, wave, 0, lane);
-        const f32x16 bias = bias_of(net.b_p[i], wave);
+        bnext = bias_of(i + 1 < D ? net.b_p[i + 1] : net.b_feat, wave);
         ncw_lds_barrier();
         const sb_lfrag* in = cur ? abuf1 : abuf0;
         sb_lfrag* out = cur ? abuf0 : abuf1;
 #pragma unroll
         for (int tp = 0; tp < SB_TILES; tp += 2) {
             f32x16 acc0 = bias, acc1 = bias;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                acc0 = NCW_MFMA_H(wa[q], in[(tp * 16 + q) * 64 + lane], acc0, 0, 0, 0);
-                acc1 = NCW_MFMA_H(wa[q], in[((tp + 1) * 16 + q) * 64 + lane], acc1, 0, 0, 0);
-            }
-            if (skip) {
-#pragma unroll
-                for (int q = 0; q < 6; ++q) {
-                    acc0 = NCW_MFMA_H(wx[q], xbuf[(tp * 6 + q) * 64 + lane], acc0, 0, 0, 0);
-                    acc1 = NCW_MFMA_H(wx[q], xbuf[((tp + 1) * 6 + q) * 64 + lane], acc1, 0, 0, 0);
-                }
-            }
+            const sb_lfrag *in0 = in + tp * 16 * 64 + lane, *in1 = in0 + 16 * 64;
+            if (tp == SB_TILES - 2) sb_mma<16, true, 16>(acc0, acc1, wa, in0, in1, wnext, 8, wave, lane);
+            else sb_mma<16, true>(acc0, acc1, wa, in0, in1);
+            if (skip) sb_mma<6, true>(acc0, acc1, wx, xbuf + tp * 6 * 64 + lane, xbuf + (tp + 1) * 6 * 64 + lane);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const f32x16 y = relu16(j ? acc1 : acc0);
@@ -408,16 +451,13 @@ __global__ __launch_bounds__(64 * SB_WAVES) void nerf_fwdB_kernel(NcwNerfNet net
                 sb_store_units(out, tp + j, wave, y, lane);
             }
         }
-#pragma unroll
-        for (int q = 0; q < 16; ++q) wa[q] = wb[q];
         cur ^= 1;
     }
     // ---- density (waves 0..3), feature layer (wa = slice of w_feat), AUX1 into xbuf -------------------------------
     const int hb = wave & 3, hp = wave >> 2;  // head job: block hb, tiles 2 hp and 2 hp + 1
+    const int ta = 2 * hp, tb = 2 * hp + 1;
     {
-        sb_load_slice<16>(wb, net.w_a[0], 4, hb, 0, lane);   // head layer 0: feature columns
-        sb_load_slice<6>(wx, net.w_a[0], 4, hb, 16, lane);   //               AUX1 columns (units 16..21)
-        const f32x16 bias = bias_of(net.b_feat, wave);
+        const f32x16 bias = bnext;
         ncw_lds_barrier();  // h_D complete in abuf[cur]; nobody reads gamma(p) in xbuf any more
         const sb_lfrag* in = cur ? abuf1 : abuf0;
         sb_lfrag* out = cur ? abuf0 : abuf1;
@@ -436,22 +476,23 @@ __global__ __launch_bounds__(64 * SB_WAVES) void nerf_fwdB_kernel(NcwNerfNet net
 #pragma unroll
                 for (int q = 0; q < 6; ++q) xbuf[(wave * 6 + q) * 64 + lane] = aux1a.f[q];
             }
+            __builtin_amdgcn_sched_barrier(0);  // (the 64 registers of w_alpha only once the AUX1 block's 48 are free again)
             bf16x8 w1[16];
             sb_load_slice<16>(w1, net.w_alpha, 1, 0, 0, lane);
             CVec<1> o;
             load_bias(o, net.b_alpha, lane);
-#pragma unroll
-            for (int q = 0; q < 16; ++q) o.v[0] = NCW_MFMA_H(w1[q], in[(wave * 16 + q) * 64 + lane], o.v[0], 0, 0, 0);
+            sb_mma<16, false>(o.v[0], o.v[0], w1, in + wave * 16 * 64 + lane, nullptr);
             if (pvalid && lane < 32) density[pp] = o.v[0][0];
         }
+        // head layer 0: its AUX1 columns (units 16..21) and bias, ahead of its feature columns, which replace wa below
+        sb_load_slice<6>(wx, net.w_a[0], 4, hb, 16, lane);
+        bnext = bias_of(net.b_a[0], hb);
 #pragma unroll
         for (int tp = 0; tp < SB_TILES; tp += 2) {
             f32x16 acc0 = bias, acc1 = bias;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                acc0 = NCW_MFMA_H(wa[q], in[(tp * 16 + q) * 64 + lane], acc0, 0, 0, 0);
-                acc1 = NCW_MFMA_H(wa[q], in[((tp + 1) * 16 + q) * 64 + lane], acc1, 0, 0, 0);
-            }
+            const sb_lfrag *in0 = in + tp * 16 * 64 + lane, *in1 = in0 + 16 * 64;
+            if (tp == SB_TILES - 2) sb_mma<16, true, 16>(acc0, acc1, wa, in0, in1, net.w_a[0], 4, hb, lane);
+            else sb_mma<16, true>(acc0, acc1, wa, in0, in1);
             if (TRAIN) {
                 stash_store_block((SE*)st.featn, (size_t)(tile0 + tp), 8, wave, acc0, lane);
                 stash_store_block((SE*)st.featn, (size_t)(tile0 + tp + 1), 8, wave, acc1, lane);
@@ -459,42 +500,47 @@ __global__ __launch_bounds__(64 * SB_WAVES) void nerf_fwdB_kernel(NcwNerfNet net
             sb_store_units(out, tp, wave, acc0, lane);
             sb_store_units(out, tp + 1, wave, acc1, lane);
         }
-#pragma unroll
-        for (int q = 0; q < 16; ++q) wa[q] = wb[q];
         cur ^= 1;
     }
     // ---- appearance head (nerf.py:131-139,173-174): layer 0 takes [feature | AUX1], the others 128 -> 128 ---------
     for (int i = 0; i < net.n_head; ++i) {
-        bf16x8 wn[8];
-        if (i + 1 < net.n_head) sb_load_slice<8>(wn, net.w_a[i + 1], 4, hb, 0, lane);
-        const f32x16 bias = bias_of(net.b_a[i], hb);
+        const bool more = i + 1 < net.n_head;
+        const f32x16 bias = bnext;
+        if (more) bnext = bias_of(net.b_a[i + 1], hb);
+        f32x16 rb0, rb1;  // head layer 0: the per-ray fp32 rows, requested ahead of the next slice
+        const bool ray_rows = (i == 0 && st.aux_bias != nullptr);
+        if (ray_rows) {
+            auto ray_row = [&](int t) {  // the addends of ncw_add_ray_bias_block
+                const f32x4* ab = reinterpret_cast<const f32x4*>(st.aux_bias + (size_t)rbuf[t * 32 + (lane & 31)] * 128) + 8 * hb + (lane >> 5);
+                f32x16 v;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const f32x4 q = ab[2 * g];
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) v[4 * g + c] = q[c];
+                }
+                return v;
+            };
+            rb0 = ray_row(ta);
+            rb1 = ray_row(tb);
+        }
         ncw_lds_barrier();
         const sb_lfrag* in = cur ? abuf1 : abuf0;
         sb_lfrag* out = cur ? abuf0 : abuf1;
-        const int ta = 2 * hp, tb = 2 * hp + 1;
+        const sb_lfrag *in0 = in + ta * 16 * 64 + lane, *in1 = in + tb * 16 * 64 + lane;
+        // (the last layer reloads its own slice: a runtime "no next slice" would double every loop below)
+        const void* wnext = net.w_a[more ? i + 1 : i];
         f32x16 acc0 = bias, acc1 = bias;
         if (i == 0) {
+            sb_mma<16, true, 8>(acc0, acc1, wa, in0, in1, wnext, 4, hb, lane);
+            if (ray_rows) {  // the AUX1 columns: per-ray fp32 rows of ncw_aux_ray_bias instead of 16-bit operands
 #pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                acc0 = NCW_MFMA_H(wa[q], in[(ta * 16 + q) * 64 + lane], acc0, 0, 0, 0);
-                acc1 = NCW_MFMA_H(wa[q], in[(tb * 16 + q) * 64 + lane], acc1, 0, 0, 0);
-            }
-            if (st.aux_bias != nullptr) {  // the AUX1 columns: per-ray fp32 rows of ncw_aux_ray_bias instead of 16-bit operands
-                ncw_add_ray_bias_block(acc0, st.aux_bias + (size_t)rbuf[ta * 32 + (lane & 31)] * 128, hb, lane);
-                ncw_add_ray_bias_block(acc1, st.aux_bias + (size_t)rbuf[tb * 32 + (lane & 31)] * 128, hb, lane);
+                for (int r = 0; r < 16; ++r) { acc0[r] += rb0[r]; acc1[r] += rb1[r]; }
             } else {
-#pragma unroll
-                for (int q = 0; q < 6; ++q) {
-                    acc0 = NCW_MFMA_H(wx[q], xbuf[(ta * 6 + q) * 64 + lane], acc0, 0, 0, 0);
-                    acc1 = NCW_MFMA_H(wx[q], xbuf[(tb * 6 + q) * 64 + lane], acc1, 0, 0, 0);
-                }
+                sb_mma<6, true>(acc0, acc1, wx, xbuf + ta * 6 * 64 + lane, xbuf + tb * 6 * 64 + lane);
             }
         } else {
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                acc0 = NCW_MFMA_H(wa[q], in[(ta * 16 + q) * 64 + lane], acc0, 0, 0, 0);
-                acc1 = NCW_MFMA_H(wa[q], in[(tb * 16 + q) * 64 + lane], acc1, 0, 0, 0);
-            }
+            sb_mma<8, true, 8>(acc0, acc1, wa, in0, in1, wnext, 4, hb, lane);
         }
         const f32x16 y0 = relu16(acc0), y1 = relu16(acc1);
         if (TRAIN) {
@@ -503,8 +549,6 @@ __global__ __launch_bounds__(64 * SB_WAVES) void nerf_fwdB_kernel(NcwNerfNet net
         }
         sb_store_units(out, ta, hb, y0, lane);
         sb_store_units(out, tb, hb, y1, lane);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) wa[q] = wn[q];
         cur ^= 1;
     }
     // ---- raw rgb (nerf.py:181), waves 0..3 ---------------------------------------------------------------------
@@ -515,8 +559,7 @@ __global__ __launch_bounds__(64 * SB_WAVES) void nerf_fwdB_kernel(NcwNerfNet net
         sb_load_slice<8>(w1, net.w_rgb, 1, 0, 0, lane);
         CVec<1> o;
         load_bias(o, net.b_rgb, lane);
-#pragma unroll
-        for (int q = 0; q < 8; ++q) o.v[0] = NCW_MFMA_H(w1[q], in[(wave * 16 + q) * 64 + lane], o.v[0], 0, 0, 0);
+        sb_mma<8, false>(o.v[0], o.v[0], w1, in + wave * 16 * 64 + lane, nullptr);
         if (pvalid && lane < 32) {
             rgb[pp * 3 + 0] = o.v[0][0];
             rgb[pp * 3 + 1] = o.v[0][1];
@@ -531,11 +574,21 @@ __global__ __launch_bounds__(64 * SB_WAVES) void nerf_fwdB_kernel(NcwNerfNet net
 // nerf_bwd_kernel (ncw_nerf.hip) -- rgb head reversed, appearance head, feature / density, trunk -- emitting the
 // z-bar stashes the weight-gradient GEMMs read and the per-ray appearance-code gradient d_a.
 // ------------------------------------------------------------------------------------------------
-NCW_DEV f32x16 sb_relu_bwd(const f32x16& u, const ncw_h16* __restrict__ st_y, size_t tile, int RB, int rb, int lane) {
-    f32x16 y, z;
-    stash_load_block(y, st_y, tile, RB, rb, lane);
+// z = relu'(h) u from the stashed post-activation h of one block, in two steps: the block's stashed activations (16 x 16 bit per lane) are requested early -- ahead of the weight
+// slice that is reloaded during the MFMAs -- and applied after them, so their wait is a counted one.
+typedef ncw_h16 sb_h4 __attribute__((ext_vector_type(4)));
+struct SbMask { sb_h4 g[4]; };
+NCW_DEV SbMask sb_mask_load(const ncw_h16* __restrict__ st_y, size_t tile, int RB, int rb, int lane) {
+    const sb_h4* p = reinterpret_cast<const sb_h4*>(st_y) + ((tile * RB + rb) * 4) * 64 + lane;
+    SbMask m;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) z[r] = y[r] > 0.f ? u[r] : 0.f;
+    for (int g = 0; g < 4; ++g) m.g[g] = NCW_STASH_LD(p[g * 64]);
+    return m;
+}
+NCW_DEV f32x16 sb_relu_bwd(const f32x16& u, const SbMask& m) {
+    f32x16 z;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) z[r] = (float)m.g[r >> 2][r & 3] > 0.f ? u[r] : 0.f;
     return z;
 }
 
@@ -599,15 +652,20 @@ __global__ __launch_bounds__(64 * SB_WAVES) void nerf_bwdB_kernel(NcwNerfNet net
         to_act(za1, zal);
         xbuf[(wave * 6 + 1) * 64 + lane] = za1.f[0];
     }
-    bf16x8 wa[16], wb[16];
+    bf16x8 wa[16];
     f32x16 zero16;
 #pragma unroll
     for (int r = 0; r < 16; ++r) zero16[r] = 0.f;
     int cur = 0;
+    // the stashed activations a ReLU derivative needs: requested BEFORE the MFMAs whose result they mask, and so before the
+    // slice reloaded during those MFMAs
+    SbMask m0, m1;
     // ---- appearance head reversed: wave = (block hb, tiles ta, tb) -------------------------------------------------
     f32x16 ue0, ue1;
     {
         const bf16x8 wr = ((gfrag)net.wt_rgb)[(size_t)hb * 64 + lane];  // wt_rgb: 4 out-blocks, unit 0 (K = 3)
+        m0 = sb_mask_load((const SE*)st.e[NH - 1], (size_t)(tile0 + ta), 4, hb, lane);
+        m1 = sb_mask_load((const SE*)st.e[NH - 1], (size_t)(tile0 + tb), 4, hb, lane);
         if (NH > 1) sb_load_slice<8>(wa, net.wt_a[NH - 1], 4, hb, 0, lane);
         else sb_load_slice<8>(wa, net.wt_a[0], 11, wave, 0, lane);
         ncw_lds_barrier();  // d_rgb / d_density units visible
@@ -616,124 +674,100 @@ __global__ __launch_bounds__(64 * SB_WAVES) void nerf_bwdB_kernel(NcwNerfNet net
     }
     for (int i = NH - 1; i >= 1; --i) {
         sb_lfrag* out = cur ? abuf1 : abuf0;
-        const f32x16 z0 = sb_relu_bwd(ue0, (const SE*)st.e[i], (size_t)(tile0 + ta), 4, hb, lane);
-        const f32x16 z1 = sb_relu_bwd(ue1, (const SE*)st.e[i], (size_t)(tile0 + tb), 4, hb, lane);
+        const f32x16 z0 = sb_relu_bwd(ue0, m0), z1 = sb_relu_bwd(ue1, m1);
         stash_store_block((SE*)st.ze[i], (size_t)(tile0 + ta), 4, hb, z0, lane);
         stash_store_block((SE*)st.ze[i], (size_t)(tile0 + tb), 4, hb, z1, lane);
         sb_store_units(out, ta, hb, z0, lane);
         sb_store_units(out, tb, hb, z1, lane);
-        if (i - 1 >= 1) sb_load_slice<8>(wb, net.wt_a[i - 1], 4, hb, 0, lane);
-        else sb_load_slice<8>(wb, net.wt_a[0], 11, wave, 0, lane);  // next: q = wt_a[0] ze_0, block = wave
+        m0 = sb_mask_load((const SE*)st.e[i - 1], (size_t)(tile0 + ta), 4, hb, lane);
+        m1 = sb_mask_load((const SE*)st.e[i - 1], (size_t)(tile0 + tb), 4, hb, lane);
+        const bool head_next = i - 1 >= 1;  // else next: q = wt_a[0] ze_0, block = wave
+        const void* wnext = head_next ? net.wt_a[i - 1] : net.wt_a[0];
+        const int sn = head_next ? 4 : 11, obn = head_next ? hb : wave;
         ncw_lds_barrier();
         ue0 = zero16; ue1 = zero16;
-#pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            ue0 = NCW_MFMA_H(wa[q], out[(ta * 16 + q) * 64 + lane], ue0, 0, 0, 0);
-            ue1 = NCW_MFMA_H(wa[q], out[(tb * 16 + q) * 64 + lane], ue1, 0, 0, 0);
-        }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) wa[q] = wb[q];
+        sb_mma<8, true, 8>(ue0, ue1, wa, out + ta * 16 * 64 + lane, out + tb * 16 * 64 + lane, wnext, sn, obn, lane);
         cur ^= 1;
     }
     // ---- ze_0, then q = wt_a[0] ze_0: blocks 0..7 = d(feature) (block = wave), blocks 8..10 = AUX1 adjoint -> d_a -----
     {
         sb_lfrag* out = cur ? abuf1 : abuf0;
-        const f32x16 z0 = sb_relu_bwd(ue0, (const SE*)st.e[0], (size_t)(tile0 + ta), 4, hb, lane);
-        const f32x16 z1 = sb_relu_bwd(ue1, (const SE*)st.e[0], (size_t)(tile0 + tb), 4, hb, lane);
+        const f32x16 z0 = sb_relu_bwd(ue0, m0), z1 = sb_relu_bwd(ue1, m1);
         stash_store_block((SE*)st.ze[0], (size_t)(tile0 + ta), 4, hb, z0, lane);
         stash_store_block((SE*)st.ze[0], (size_t)(tile0 + tb), 4, hb, z1, lane);
         sb_store_units(out, ta, hb, z0, lane);
         sb_store_units(out, tb, hb, z1, lane);
-        sb_load_slice<16>(wb, net.wt_feat, 8, wave, 0, lane);  // next: u = wt_feat zf
+        // next: u = wt_feat zf.  Units 8..15 of wa are free already, units 0..7 follow during the last tile pair below
+        sb_load_slice<8>(wa + 8, net.wt_feat, 8, wave, 8, lane);
+        bf16x8 wq[8];
+        sb_load_slice<8>(wq, net.wt_a[0], 11, 8 + wave % 3, 0, lane);  // the wave's first AUX1 job below
         ncw_lds_barrier();
         const sb_lfrag* in = out;
         sb_lfrag* out2 = cur ? abuf0 : abuf1;
-#pragma unroll
-        for (int tp = 0; tp < SB_TILES; tp += 2) {
-            f32x16 a0 = zero16, a1 = zero16;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) {
-                a0 = NCW_MFMA_H(wa[q], in[(tp * 16 + q) * 64 + lane], a0, 0, 0, 0);
-                a1 = NCW_MFMA_H(wa[q], in[((tp + 1) * 16 + q) * 64 + lane], a1, 0, 0, 0);
-            }
-            stash_store_block((SE*)st.zfeat, (size_t)(tile0 + tp), 8, wave, a0, lane);
-            stash_store_block((SE*)st.zfeat, (size_t)(tile0 + tp + 1), 8, wave, a1, lane);
-            sb_store_units(out2, tp, wave, a0, lane);
-            sb_store_units(out2, tp + 1, wave, a1, lane);
-        }
-        // the 3 AUX1 blocks x 4 tiles = 12 jobs: wave w takes jobs w and w + 8
+        // the 3 AUX1 blocks x 4 tiles = 12 jobs: wave w takes jobs w and w + 8 (ahead of the tile pairs: their weights then
+        // precede the reloaded slice in the memory pipe)
         for (int j = wave; j < 12; j += SB_WAVES) {
             const int b = j % 3, t = j / 3;
-            bf16x8 wq[8];
-            sb_load_slice<8>(wq, net.wt_a[0], 11, 8 + b, 0, lane);
-            f32x16 qa = zero16;
-#pragma unroll
-            for (int q = 0; q < 8; ++q) qa = NCW_MFMA_H(wq[q], in[(t * 16 + q) * 64 + lane], qa, 0, 0, 0);
+            if (j != wave) sb_load_slice<8>(wq, net.wt_a[0], 11, 8 + b, 0, lane);
             int64_t p = (tile0 + t) * 32 + (lane & 31);
             const bool valid = p < n;
             if (!valid) p = n - 1;
             p = point_slot(src, p);
             const int64_t ray = (src.mode == 0) ? p : p / src.per_ray;
+            f32x16 qa = zero16;
+            sb_mma<8, false>(qa, qa, wq, in + t * 16 * 64 + lane, nullptr);
             sb_accumulate_d_a(b, qa, d_a, ray, net.n_a, valid, lane);
         }
 #pragma unroll
-        for (int q = 0; q < 16; ++q) wa[q] = wb[q];
+        for (int tp = 0; tp < SB_TILES; tp += 2) {
+            f32x16 a0 = zero16, a1 = zero16;
+            const sb_lfrag *in0 = in + tp * 16 * 64 + lane, *in1 = in0 + 16 * 64;
+            if (tp == SB_TILES - 2) sb_mma<8, true, 8>(a0, a1, wa, in0, in1, net.wt_feat, 8, wave, lane);
+            else sb_mma<8, true>(a0, a1, wa, in0, in1);
+            stash_store_block((SE*)st.zfeat, (size_t)(tile0 + tp), 8, wave, a0, lane);
+            stash_store_block((SE*)st.zfeat, (size_t)(tile0 + tp + 1), 8, wave, a1, lane);
+            sb_store_units(out2, tp, wave, a0, lane);
+            sb_store_units(out2, tp + 1, wave, a1, lane);
+        }
         cur ^= 1;  // zf lives in out2
     }
-    // ---- u = wt_feat zf + wt_alpha d_density;  za_{D-1} = relu'(h_D) u --------------------------------------------
-    {
-        const bf16x8 wal = ((gfrag)net.wt_alpha)[(size_t)wave * 64 + lane];  // wt_alpha: 8 out-blocks, unit 0 (K = 1)
-        if (D - 1 > 0) sb_load_slice<16>(wb, net.wt_p[D - 1], (D - 1 == net.skip + 1) ? 11 : 8, wave, 0, lane);
-        ncw_lds_barrier();  // zf complete
-        const sb_lfrag* in = cur ? abuf1 : abuf0;
-        sb_lfrag* out = cur ? abuf0 : abuf1;
-#pragma unroll
-        for (int tp = 0; tp < SB_TILES; tp += 2) {
-            f32x16 u0 = zero16, u1 = zero16;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                u0 = NCW_MFMA_H(wa[q], in[(tp * 16 + q) * 64 + lane], u0, 0, 0, 0);
-                u1 = NCW_MFMA_H(wa[q], in[((tp + 1) * 16 + q) * 64 + lane], u1, 0, 0, 0);
-            }
-            u0 = NCW_MFMA_H(wal, xbuf[(tp * 6 + 1) * 64 + lane], u0, 0, 0, 0);
-            u1 = NCW_MFMA_H(wal, xbuf[((tp + 1) * 6 + 1) * 64 + lane], u1, 0, 0, 0);
-            const f32x16 z0 = sb_relu_bwd(u0, (const SE*)st.h[D], (size_t)(tile0 + tp), 8, wave, lane);
-            const f32x16 z1 = sb_relu_bwd(u1, (const SE*)st.h[D], (size_t)(tile0 + tp + 1), 8, wave, lane);
-            stash_store_block((SE*)st.zp[D - 1], (size_t)(tile0 + tp), 8, wave, z0, lane);
-            stash_store_block((SE*)st.zp[D - 1], (size_t)(tile0 + tp + 1), 8, wave, z1, lane);
-            sb_store_units(out, tp, wave, z0, lane);
-            sb_store_units(out, tp + 1, wave, z1, lane);
-        }
-#pragma unroll
-        for (int q = 0; q < 16; ++q) wa[q] = wb[q];
-        cur ^= 1;
-    }
-    // ---- trunk reversed: za_{i-1} = relu'(h_i) (wt_p[i] za_i), i = D-1 .. 1 (wa = slice of wt_p[i]) ----------------------
-    for (int i = D - 1; i >= 1; --i) {
-        if (i - 1 >= 1) sb_load_slice<16>(wb, net.wt_p[i - 1], (i - 1 == net.skip + 1) ? 11 : 8, wave, 0, lane);
+    // One trunk-side sweep: z = relu'(h) (wa . in [+ wt_alpha d_density]) for the two tile pairs, z stashed as zp and (store) handed
+    // on through LDS; the next slice (wnext) replaces wa during the last pair.
+    auto sweep = [&](const SE* st_h, SE* st_z, const bf16x8* wal, const void* wnext, int sn, bool store) __attribute__((always_inline)) {
         ncw_lds_barrier();
         const sb_lfrag* in = cur ? abuf1 : abuf0;
         sb_lfrag* out = cur ? abuf0 : abuf1;
 #pragma unroll
         for (int tp = 0; tp < SB_TILES; tp += 2) {
+            m0 = sb_mask_load(st_h, (size_t)(tile0 + tp), 8, wave, lane);
+            m1 = sb_mask_load(st_h, (size_t)(tile0 + tp + 1), 8, wave, lane);
             f32x16 u0 = zero16, u1 = zero16;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                u0 = NCW_MFMA_H(wa[q], in[(tp * 16 + q) * 64 + lane], u0, 0, 0, 0);
-                u1 = NCW_MFMA_H(wa[q], in[((tp + 1) * 16 + q) * 64 + lane], u1, 0, 0, 0);
+            const sb_lfrag *in0 = in + tp * 16 * 64 + lane, *in1 = in0 + 16 * 64;
+            if (tp == SB_TILES - 2) sb_mma<16, true, 16>(u0, u1, wa, in0, in1, wnext, sn, wave, lane);
+            else sb_mma<16, true>(u0, u1, wa, in0, in1);
+            if (wal != nullptr) {
+                u0 = NCW_MFMA_H(*wal, xbuf[(tp * 6 + 1) * 64 + lane], u0, 0, 0, 0);
+                u1 = NCW_MFMA_H(*wal, xbuf[((tp + 1) * 6 + 1) * 64 + lane], u1, 0, 0, 0);
             }
-            const f32x16 z0 = sb_relu_bwd(u0, (const SE*)st.h[i], (size_t)(tile0 + tp), 8, wave, lane);
-            const f32x16 z1 = sb_relu_bwd(u1, (const SE*)st.h[i], (size_t)(tile0 + tp + 1), 8, wave, lane);
-            stash_store_block((SE*)st.zp[i - 1], (size_t)(tile0 + tp), 8, wave, z0, lane);
-            stash_store_block((SE*)st.zp[i - 1], (size_t)(tile0 + tp + 1), 8, wave, z1, lane);
-            if (i - 1 >= 1) {
+            const f32x16 z0 = sb_relu_bwd(u0, m0), z1 = sb_relu_bwd(u1, m1);
+            stash_store_block(st_z, (size_t)(tile0 + tp), 8, wave, z0, lane);
+            stash_store_block(st_z, (size_t)(tile0 + tp + 1), 8, wave, z1, lane);
+            if (store) {
                 sb_store_units(out, tp, wave, z0, lane);
                 sb_store_units(out, tp + 1, wave, z1, lane);
             }
         }
-#pragma unroll
-        for (int q = 0; q < 16; ++q) wa[q] = wb[q];
         cur ^= 1;
+    };
+    // ---- u = wt_feat zf + wt_alpha d_density;  za_{D-1} = relu'(h_D) u --------------------------------------------
+    {
+        const bf16x8 wal = ((gfrag)net.wt_alpha)[(size_t)wave * 64 + lane];  // wt_alpha: 8 out-blocks, unit 0 (K = 1)
+        sweep((const SE*)st.h[D], (SE*)st.zp[D - 1], &wal, net.wt_p[D - 1], (D - 1 == net.skip + 1) ? 11 : 8, true);  // (barrier: zf complete)
+    }
+    // ---- trunk reversed: za_{i-1} = relu'(h_i) (wt_p[i] za_i), i = D-1 .. 1 (wa = slice of wt_p[i]) ----------------------
+    for (int i = D - 1; i >= 1; --i) {
+        const int ln = i - 1 >= 1 ? i - 1 : i;  // (the last sweep reloads its own slice: a runtime "no next slice" would double the loop)
+        sweep((const SE*)st.h[i], (SE*)st.zp[i - 1], nullptr, net.wt_p[ln], (ln == net.skip + 1) ? 11 : 8, i - 1 >= 1);
     }
 }
 
