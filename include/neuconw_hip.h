@@ -858,6 +858,76 @@ int ncw_surf_sample(const double* verts, const int32_t* faces, const double* cdf
                     int64_t n, int64_t n_total, int mode, double* pts, int32_t* tri, double* urr, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Exact point-to-triangle-mesh distances (csrc/ncw_ptm.hip): the recall side of the mesh evaluation measured to the
+ * predicted SURFACE, not to samples of it (what trimesh `proximity`, kaolin `point_to_mesh_distance` or open3d
+ * `RaycastingScene` answer; no parity with any of them is pinned: none is at hand).  The uniform-grid shell search of
+ * ncw_nn_*, carried from points to triangles.  All arithmetic is float64 on coordinates recentred in float64; products and
+ * sums are rounded one by one (no FMA), so tests/_ptm_ref.py restates the same arithmetic.
+ * DISTANCE CONTRACT.  Query P, triangle (A, B, C):
+ *   face term : n = (B-A)x(C-A), nn = n.n; exists iff nn > 0, nn finite and the three edge functions ((B-A)x(P-A)).n,
+ *               ((C-B)x(P-B)).n, ((A-C)x(P-C)).n are all >= 0; d^2 = t^2 / nn with t = n.(P-A); closest = P - (t/nn) n.
+ *   segments  : AB, BC, CA, endpoints in CANONICAL order (the lexicographically smaller coordinate triple is U, the other
+ *               V; equal endpoints stay): w = V-U, l = w.w, s = l > 0 ? clamp(((P-U).w)/l, 0, 1) : 0; closest c = U if
+ *               s <= 0, V if s >= 1, else U + s w; d^2 = |P-c|^2 from the coordinate differences.
+ *   triangle  : the minimum of the terms that exist; closest point of the FIRST minimal term in the order face, AB, BC, CA.
+ *               Degenerate triangles need no special case (the face term drops out).
+ *   mesh      : the minimum over the VALID triangles, ties on equal d^2 to the SMALLER triangle index.  Valid: all three
+ *               corner indices in [0, n_verts), all nine coordinates finite and, with a box (HOST double[6]: lo xyz, hi xyz, in
+ *               the coordinates of verts; NULL = none), all three corners inside the closed box (ncw_surf_weights' rule).
+ *               An invalid triangle's corners are never read and it is never returned.
+ * Canonical endpoints make a shared edge or vertex give bit-identical d^2 from every triangle that owns it.
+ * GRID.  Cubic cells of side h over [lo, lo + dim h); cell = clamp(floor((x - lo) inv_h), 0, dim - 1) per axis, linear key
+ * (cx dim[1] + cy) dim[2] + cz (x slowest).  A triangle belongs to every cell its axis-aligned box overlaps (cell range
+ * clamped into the grid); one whose box covers more than max_cells_per_tri cells stays out of the grid (large list).
+ *   ncw_ptm_pack      : tri [F][9] f64 = the recentred corners (A, B, C) minus centre (HOST double[3]) of faces [F,3] int32 over
+ *                       verts [V,3] f64; valid [F] uint8.  Invalid rows of tri are zero.
+ *   ncw_ptm_count     : count [F] int32 = cells of the triangle's box, or 0 when it is invalid or large;
+ *                       large [F] uint8 = 1 for a valid triangle with more than max_cells_per_tri (1 .. 2^30) cells.
+ *   (caller)          : cum = inclusive prefix sum of count in int64 (torch.cumsum); n_pairs = cum[F-1] <= 2^31 - 1.
+ *   ncw_ptm_emit      : keys [n_pairs] int32 / ids [n_pairs] int32: pair cum[f] - count[f] + k = (k-th cell, f).
+ *   (caller)          : stable sort of the pairs by key (torch.sort): sorted_keys, order.
+ *   ncw_ptm_ranges    : cell_range [n_cells][2] int32 (ZEROED by the caller) gets [start, end) of every non-empty cell;
+ *                       sorted_ids [n_pairs] int32 = ids in cell order.
+ *   ncw_ptm_cell_keys : keys [n] int32 of n recentred queries q [n,3] f64.
+ *   ncw_ptm_query     : one lane per query in cell order (q_order: stable sort of the query keys).  The large list
+ *                       (large_ids [n_large] int32, may be NULL when n_large == 0) is tested first, staged through LDS; then
+ *                       Chebyshev shells r = 0, 1, .. around the query's cell, stopping after shell r once
+ *                       best d^2 < (b - margin)^2 (b = distance to the faces of the (2r+1)^3 block not on the grid boundary:
+ *                       an unvisited triangle's box does not overlap the block, so it lies beyond one of them) or once the
+ *                       block covers the grid.  Outputs at the query's ORIGINAL position: dist [n] f64 = sqrt(d^2), idx [n]
+ *                       int64, closest [n,3] f64 (NULL = not written).  Queries still open after max_shell shells are
+ *                       appended to escaped [n] int32 (their count in *n_escaped, zeroed by the caller) and left unwritten.
+ *   ncw_ptm_brute     : the escaped queries against all valid triangles (LDS tiles, triangles split over blocks): a 64-bit
+ *                       atomicMin of the bits of d^2 (>= 0: ordered like the value), a second pass with an atomicMin of the
+ *                       index among the triangles at that minimum, a finish pass writing the outputs.  scratch:
+ *                       uint64 [2 n_esc].  A query that no triangle answers (NaN coordinates) gets dist +inf, idx -1.
+ * No float atomics: results are bitwise reproducible, and identical for any split of the queries into launches.
+ * All return NCW_E_BADARG for NULL pointers, a bad grid (h, inv_h not > 0, dim < 1, more than 2^30 cells) or counts out of
+ * range (n_faces, n_pairs, n_esc > 2^31 - 1, n_verts < 0, max_shell < 0, margin not >= 0); 0 without a launch for an empty range.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct NcwPtmGrid {
+    double lo[3];
+    double h, inv_h;
+    int32_t dim[3];
+} NcwPtmGrid;
+
+int ncw_ptm_pack(const double* verts, int64_t n_verts, const int32_t* faces, int64_t n_faces, const double* centre,
+                 const double* box, double* tri, uint8_t* valid, void* stream);
+int ncw_ptm_count(const double* tri, const uint8_t* valid, int64_t n_faces, const NcwPtmGrid* grid, int64_t max_cells_per_tri,
+                  int32_t* count, uint8_t* large, void* stream);
+int ncw_ptm_emit(const double* tri, const int32_t* count, const int64_t* cum, int64_t n_faces, const NcwPtmGrid* grid,
+                 int64_t n_pairs, int32_t* keys, int32_t* ids, void* stream);
+int ncw_ptm_ranges(const int32_t* sorted_keys, const int64_t* order, const int32_t* ids, int64_t n_pairs, int64_t n_cells,
+                   int32_t* cell_range, int32_t* sorted_ids, void* stream);
+int ncw_ptm_cell_keys(const double* q, int64_t n, const NcwPtmGrid* grid, int32_t* keys, void* stream);
+int ncw_ptm_query(const double* tri, int64_t n_faces, const int32_t* cell_range, const int32_t* sorted_ids,
+                  const int32_t* large_ids, int64_t n_large, const double* q, const int64_t* q_order, int64_t n,
+                  const NcwPtmGrid* grid, int max_shell, double margin, double* dist, int64_t* idx, double* closest,
+                  int32_t* escaped, int32_t* n_escaped, void* stream);
+int ncw_ptm_brute(const double* tri, const uint8_t* valid, int64_t n_faces, const double* q, int64_t n, const int32_t* escaped,
+                  int64_t n_esc, uint64_t* scratch, double* dist, int64_t* idx, double* closest, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * View selection (csrc/ncw_roi.hip): the region-of-interest test of the split writer, for ALL registered views of a scene in
  * one launch.  The reference runs it per image (tools/prepare_data/dataset_filter_utils.py:160-178: get_ray_directions +
  * get_rays + eight torch ops, after a full decode of the image that is only used for its size); it needs no per-pixel input.

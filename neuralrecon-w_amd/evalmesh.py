@@ -20,6 +20,12 @@ mesh is scored by k |GT| points drawn uniformly by area from its triangles insid
 (`visualize_error`, eval_utils.py:116-123).  Unpinned against open3d, whose source is not at hand: its crop rule (taken from
 its documentation), its Mersenne-twister stream (unseeded in the reference: not reproducible there either; ours is
 Philox4x32-10 of (sample index, seed)) and its double -> uchar colour rounding.
+
+`eval_mesh(exact_recall=True)` measures the recall side -- GT point to prediction -- to the predicted SURFACE itself: exact
+point-to-triangle distances in float64 over a uniform grid of triangles (csrc/ncw_ptm.hip, `TriGrid`, `mesh_distances`),
+instead of the distance to the nearest vertex or sample, which is always too large.  The reference has no such mode; what
+users know it from is trimesh `proximity`, kaolin `point_to_mesh_distance` or open3d `RaycastingScene`, none of which is at
+hand: parity with them is unpinned.
 """
 import ctypes as C
 import json
@@ -438,6 +444,201 @@ def sample_surface(verts, faces, n, seed=0, mode="stratified", box=None, return_
 
 
 # ---------------------------------------------------------------------------------------------------
+# exact point-to-mesh distances (csrc/ncw_ptm.hip)
+# ---------------------------------------------------------------------------------------------------
+F64_EPS = float(np.finfo(np.float64).eps)
+PTM_MAX_PAIRS = (1 << 31) - 1      # (cell, triangle) pairs of one grid: int32 positions in the cell table
+PTM_MAX_CELLS_PER_TRI = 512        # a triangle whose box covers more cells goes to the large list
+PTM_NO_LARGE = 1 << 30             # max_cells_per_tri that keeps every triangle in the grid (a grid has at most 2^24 cells)
+
+
+def ptm_centre(verts, query):
+    """The centre `mesh_distances` recentres by: `recentre`'s -- the centre of the common box of both point sets, in float64
+    -- over the rows that are finite (a NaN vertex makes its triangles invalid, it must not poison the centre), and without
+    the cast to f32.  Tensors on any device.  Returns (centre float64 numpy [3], largest |recentred coordinate|)."""
+    sets = []
+    for t in (verts, query):
+        t = t.reshape(-1, 3).double()
+        t = t[torch.isfinite(t).all(-1)]
+        if t.shape[0]:
+            sets.append(t)
+    if not sets:
+        return np.zeros(3), 0.0
+    lo = torch.stack([t.amin(0) for t in sets]).amin(0).cpu().numpy()
+    hi = torch.stack([t.amax(0) for t in sets]).amax(0).cpu().numpy()
+    centre = (lo + hi) / 2.0
+    c = torch.from_numpy(centre).to(sets[0].device)
+    return centre, max(float((t - c).abs().amax()) for t in sets)
+
+
+class TriGrid:
+    """The triangles of a mesh (verts float64 [V,3], faces int32 [F,3], device tensors, in the caller's coordinates) packed,
+    recentred by `centre` (float64 [3]) and binned on a uniform grid of cubic cells over the box of the valid triangles: a
+    triangle belongs to every cell its axis-aligned box overlaps; one over more than `max_cells_per_tri` cells goes to the
+    large list that every query tests first.  Validity as ncw_ptm_pack: corner indices in range, finite corners, and with
+    `box` all three corners inside the closed box.  The cell side is twice the median box size of the triangles, raised
+    until the table has at most MAX_CELLS cells, and doubled (rebuild) while the pair count would pass 2^31 - 1;
+    `target_cells` fixes the table size instead (tests).  `coord_max`: the largest |recentred coordinate| of the mesh and
+    the queries (sets the rounding margin of the stop test).  Built once, queried with `query`.  ValueError when no
+    triangle is valid."""
+
+    def __init__(self, verts, faces, centre, coord_max, box=None, max_shell=MAX_SHELL, target_cells=None, max_cells_per_tri=None):
+        if not (verts.is_cuda and faces.is_cuda):
+            raise L.NeuconwHipError("evalmesh.TriGrid: the mesh is not on a GPU; there is no CPU fallback")
+        assert verts.dtype == torch.float64 and faces.dtype == torch.int32
+        lib = L.get_lib()
+        self.dev = verts.device
+        verts, faces = verts.reshape(-1, 3).contiguous(), faces.reshape(-1, 3).contiguous()
+        self.n_faces = int(faces.shape[0])
+        if self.n_faces >= (1 << 31):
+            raise ValueError("at most 2^31 - 1 faces")
+        self.centre = np.ascontiguousarray(centre, dtype=np.float64).reshape(3)
+        self.centre_t = torch.from_numpy(self.centre).to(self.dev)
+        self.max_shell = int(max_shell)
+        self.max_cells_per_tri = PTM_MAX_CELLS_PER_TRI if max_cells_per_tri is None else int(max_cells_per_tri)
+        self.tri = torch.empty(self.n_faces, 9, dtype=torch.float64, device=self.dev)
+        self.valid = torch.empty(self.n_faces, dtype=torch.uint8, device=self.dev)
+        s = L.stream_ptr(self.dev)
+        L.check(lib.ncw_ptm_pack(L.ptr(verts), verts.shape[0], L.ptr(faces), self.n_faces, (C.c_double * 3)(*self.centre.tolist()),
+                                 _box6(box), L.ptr(self.tri), L.ptr(self.valid), s), "ncw_ptm_pack")
+        ok = self.valid.bool()
+        self.n_valid = int(ok.sum()) if self.n_faces else 0
+        if self.n_valid == 0:
+            raise ValueError("no valid triangle (corner indices in range, finite corners, all three corners inside the box)")
+        t3 = self.tri.view(-1, 3, 3)[ok]
+        tmin, tmax = t3.amin(1), t3.amax(1)
+        lo, hi = tmin.amin(0), tmax.amax(0)
+        self.lo = [float(v) for v in lo.tolist()]
+        self.ext = [float(b) - float(a) for a, b in zip(lo.tolist(), hi.tolist())]
+        size = (tmax - tmin).amax(1)
+        size = size[:: max(1, size.shape[0] // 65536)]
+        h_tri = 2.0 * float(size.median())
+        # rounding of the cell assignment, of the face distances and of d^2 is of order eps * (|x| + extent): the stop test
+        # keeps that much in hand
+        self.margin = 16 * F64_EPS * (float(coord_max) + max(self.ext) + 1e-300)
+        if target_cells is not None:
+            h = _grid_for(self.ext, target_cells)[0]
+        else:
+            h = max(_grid_for(self.ext, MAX_CELLS)[0], h_tri) if h_tri > 0.0 else _grid_for(self.ext, self.n_valid)[0]
+        while not self._build(h):
+            h *= 2.0
+
+    def _build(self, h):
+        """Bins the triangles on cells of side h; False (nothing kept) when the pair count passes PTM_MAX_PAIRS."""
+        lib, s = L.get_lib(), L.stream_ptr(self.dev)
+        dims = _grid_dims(self.ext, h)
+        g = L.NcwPtmGrid()
+        for a in range(3):
+            g.lo[a], g.dim[a] = self.lo[a], dims[a]
+        g.h, g.inv_h = h, 1.0 / h
+        count = torch.empty(self.n_faces, dtype=torch.int32, device=self.dev)
+        large = torch.empty(self.n_faces, dtype=torch.uint8, device=self.dev)
+        L.check(lib.ncw_ptm_count(L.ptr(self.tri), L.ptr(self.valid), self.n_faces, C.byref(g), self.max_cells_per_tri,
+                                  L.ptr(count), L.ptr(large), s), "ncw_ptm_count")
+        cum = torch.cumsum(count, 0, dtype=torch.int64).contiguous()
+        pairs = int(cum[-1])  # one device -> host read: the size of the pair list
+        if pairs > PTM_MAX_PAIRS:
+            return False
+        self.h, self.dims, self.cgrid, self.pairs = h, dims, g, pairs
+        self.ncells = int(dims[0] * dims[1] * dims[2])
+        self.large_ids = torch.nonzero(large).reshape(-1).int().contiguous()
+        self.n_large = int(self.large_ids.shape[0])
+        self.range = torch.zeros(self.ncells, 2, dtype=torch.int32, device=self.dev)
+        self.ids = torch.empty(pairs, dtype=torch.int32, device=self.dev)
+        if pairs:
+            keys = torch.empty(pairs, dtype=torch.int32, device=self.dev)
+            ids = torch.empty(pairs, dtype=torch.int32, device=self.dev)
+            L.check(lib.ncw_ptm_emit(L.ptr(self.tri), L.ptr(count), L.ptr(cum), self.n_faces, C.byref(g), pairs, L.ptr(keys),
+                                     L.ptr(ids), s), "ncw_ptm_emit")
+            skeys, order = torch.sort(keys, stable=True)
+            L.check(lib.ncw_ptm_ranges(L.ptr(skeys.contiguous()), L.ptr(order.contiguous()), L.ptr(ids), pairs, self.ncells,
+                                       L.ptr(self.range), L.ptr(self.ids), s), "ncw_ptm_ranges")
+        return True
+
+    def query(self, points64, return_closest=False, stats=None):
+        """(dist [N] float64, tri [N] int64[, closest [N,3] float64]) of every point (float64 [N,3] on the device, in the
+        caller's coordinates) to the surface; closest points come back in the caller's coordinates.  stats (dict) gets
+        `dims`, `cells`, `pairs`, `large` and adds up `escaped`."""
+        lib, s = L.get_lib(), L.stream_ptr(self.dev)
+        n = int(points64.shape[0])
+        q = (points64.reshape(-1, 3).double() - self.centre_t).contiguous()
+        dist = torch.empty(n, dtype=torch.float64, device=self.dev)
+        idx = torch.empty(n, dtype=torch.int64, device=self.dev)
+        closest = torch.empty(n, 3, dtype=torch.float64, device=self.dev) if return_closest else None
+        ne = 0
+        if n:
+            keys = torch.empty(n, dtype=torch.int32, device=self.dev)
+            L.check(lib.ncw_ptm_cell_keys(L.ptr(q), n, C.byref(self.cgrid), L.ptr(keys), s), "ncw_ptm_cell_keys")
+            q_order = torch.sort(keys, stable=True)[1].contiguous()
+            escaped = torch.empty(n, dtype=torch.int32, device=self.dev)
+            n_esc = torch.zeros(1, dtype=torch.int32, device=self.dev)
+            L.check(lib.ncw_ptm_query(L.ptr(self.tri), self.n_faces, L.ptr(self.range), L.ptr(self.ids), L.ptr(self.large_ids),
+                                      self.n_large, L.ptr(q), L.ptr(q_order), n, C.byref(self.cgrid), self.max_shell,
+                                      float(self.margin), L.ptr(dist), L.ptr(idx), L.ptr(closest), L.ptr(escaped), L.ptr(n_esc),
+                                      s), "ncw_ptm_query")
+            ne = int(n_esc.item())  # one device -> host read: the size of the escape launch
+            if ne:
+                scratch = torch.empty(2 * ne, dtype=torch.int64, device=self.dev)
+                L.check(lib.ncw_ptm_brute(L.ptr(self.tri), L.ptr(self.valid), self.n_faces, L.ptr(q), n, L.ptr(escaped), ne,
+                                          L.ptr(scratch), L.ptr(dist), L.ptr(idx), L.ptr(closest), s), "ncw_ptm_brute")
+        if stats is not None:
+            stats.update(dims=list(self.dims), cells=self.ncells, pairs=self.pairs, large=self.n_large)
+            stats["escaped"] = stats.get("escaped", 0) + ne
+        if return_closest:
+            return dist, idx, closest + self.centre_t
+        return dist, idx
+
+
+def _mesh_tensors(verts, faces, dev):
+    """(float64 [V,3], int32 [F,3]) on the device; faces of an INTEGER dtype, indices that do not fit stay out of range."""
+    f = faces if torch.is_tensor(faces) else torch.as_tensor(np.asarray(faces))
+    if f.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8) or f.dim() != 2 or f.shape[1] != 3:
+        raise ValueError("faces: an integer array of shape [F,3] (got %s %s)" % (f.dtype, tuple(f.shape)))
+    v = verts if torch.is_tensor(verts) else torch.from_numpy(np.ascontiguousarray(verts, dtype=np.float64))
+    v = v.detach().reshape(-1, 3).to(dev).double().contiguous()
+    f = f.detach().to(dev).long()
+    if f.shape[0] >= (1 << 31):
+        raise ValueError("at most 2^31 - 1 faces")
+    f = torch.where((f < 0) | (f >= v.shape[0]), torch.full_like(f, -1), f).int().contiguous()
+    return v, f
+
+
+@torch.no_grad()
+def mesh_distances(verts, faces, query, box=None, return_closest=False, chunk=None, stats=None, max_shell=MAX_SHELL,
+                   target_cells=None, max_cells_per_tri=None):
+    """For every query point its exact Euclidean distance to the SURFACE of a triangle mesh, the triangle that realises it
+    and, with `return_closest`, the closest point on it -- float64, ties on equal d^2 to the smaller triangle index (the
+    distance contract of include/neuconw_hip.h; what trimesh `proximity`, kaolin `point_to_mesh_distance` or open3d
+    `RaycastingScene` answer, none of them pinned).  verts [V,3] and query [N,3] (numpy or tensor; used as float64), faces
+    [F,3] of an integer dtype.  A triangle counts when its corner indices lie in [0, V), its corners are finite and -- with
+    `box` = [lo, hi] -- all three corners are inside the closed box (`surface_weights`' rule: the sampled precision side and
+    the exact recall side see the same surface).  Returns (dist [N] float64, tri [N] int64[, closest [N,3] float64]) on the
+    device; empty results for an empty query; ValueError when no triangle is valid.  `chunk`: queries per launch (None =
+    one launch); results are bit-identical for any chunk.  stats (dict) gets `dims`, `cells`, `pairs`, `large`, `escaped`.
+    max_shell / target_cells / max_cells_per_tri: see `TriGrid`.  No CPU fallback: NeuconwHipError without a GPU."""
+    dev = None
+    for t in (verts, query):
+        if dev is None and torch.is_tensor(t) and t.is_cuda:
+            dev = t.device
+    dev = _cuda_device(dev, "mesh_distances")
+    v, f = _mesh_tensors(verts, faces, dev)
+    q = query if torch.is_tensor(query) else torch.from_numpy(np.ascontiguousarray(query, dtype=np.float64))
+    q = q.detach().reshape(-1, 3).to(dev).double().contiguous()
+    n = int(q.shape[0])
+    if n == 0:
+        out = (torch.zeros(0, dtype=torch.float64, device=dev), torch.zeros(0, dtype=torch.int64, device=dev))
+        return out + (torch.zeros(0, 3, dtype=torch.float64, device=dev),) if return_closest else out
+    centre, cmax = ptm_centre(v, q)
+    grid = TriGrid(v, f, centre, cmax, box=box, max_shell=max_shell, target_cells=target_cells,
+                   max_cells_per_tri=max_cells_per_tri)
+    step = n if chunk is None else max(1, int(chunk))
+    parts = [grid.query(q[i0:i0 + step], return_closest, stats) for i0 in range(0, n, step)]
+    if len(parts) == 1:
+        return parts[0]
+    return tuple(torch.cat([p[k] for p in parts]) for k in range(len(parts[0])))
+
+
+# ---------------------------------------------------------------------------------------------------
 # error-coloured clouds (utils/eval_utils.py:116-123 `visualize_error`)
 # ---------------------------------------------------------------------------------------------------
 # matplotlib's "jet": piecewise-linear (x, y) nodes per channel
@@ -493,7 +694,8 @@ def _write_points(path, pts):
 
 
 def eval_mesh(file_pred, file_trgt, scene_config, is_mesh, threshold=.1, bbx_name="eval_bbx", save_name="eval", sfm=None,
-              device=None, verbose=True, surface=None, surface_seed=0, surface_mode="stratified", error_clouds=None):
+              device=None, verbose=True, surface=None, surface_seed=0, surface_mode="stratified", error_clouds=None,
+              exact_recall=False):
     """utils/eval_mesh.py:48-123 with use_o3d=False: load both PLYs (ply.read_points; `is_mesh` is accepted and, as in the
     reference's trimesh branch, not used), carry the prediction to GT coordinates by scene_config['sfm2gt'], crop both to
     scene_config[bbx_name], optionally crop both to the voxels of the filtered SfM points, nearest neighbours in both
@@ -513,7 +715,15 @@ def eval_mesh(file_pred, file_trgt, scene_config, is_mesh, threshold=.1, bbx_nam
 
     `error_clouds`: None, True (every threshold) or a list of thresholds: writes visualize/<t:.2f>/error_pred_precision.ply
     (the predicted points coloured by their distance to GT) and error_gt_recal.ply (the GT points by their distance to the
-    prediction), colours by `error_colours` (utils/eval_mesh.py:96-98)."""
+    prediction), colours by `error_colours` (utils/eval_mesh.py:96-98).
+
+    `exact_recall` (default off) measures the recall side to the predicted SURFACE: file_pred must have faces, and the GT ->
+    prediction distances (`dist2`, `recal`, error_gt_recal.ply) are exact point-to-triangle distances (`mesh_distances`) to
+    the triangles with all three corners inside the closed box -- the surface the samples of `surface=k` are drawn from.
+    The precision side is unchanged (samples with `surface=k`, vertices otherwise).  One difference from the sampled path
+    under the SfM crop: the GT queries are cropped to the SfM voxels as always, the triangles are NOT clipped to them (a
+    triangle is not a point: it may cross voxels), so a GT point may be matched to surface that the sampled path would have
+    cropped away.  metrics.json then carries "recal_mode": "exact"; with the option off every written byte is as before."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     save_dir = os.path.join(os.path.dirname(file_pred), "eval_" + str(save_name))
     os.makedirs(save_dir, exist_ok=True)
@@ -535,6 +745,11 @@ def eval_mesh(file_pred, file_trgt, scene_config, is_mesh, threshold=.1, bbx_nam
                                     mode=surface_mode, box=scene_config[bbx_name], device=dev)
         log("surface samples: %d" % verts_pred.shape[0])
         ply.write(os.path.join(save_dir, "down_pred_in_gt.ply"), verts_pred.cpu().numpy())
+    if exact_recall:
+        if surface is None:
+            m_verts, m_faces, _ = ply.read_mesh(file_pred)
+        if m_faces.shape[0] == 0:
+            raise ValueError("%s has no faces: exact recall needs a triangle mesh (exact_recall=False scores points)" % file_pred)
 
     if sfm is None and "sfm_path" in scene_config:
         sfm = {"path": scene_config["sfm_path"], "track_length": scene_config["eval_tl"],
@@ -553,7 +768,10 @@ def eval_mesh(file_pred, file_trgt, scene_config, is_mesh, threshold=.1, bbx_nam
 
     p = verts_pred if torch.is_tensor(verts_pred) else torch.from_numpy(verts_pred).to(dev)
     g = torch.from_numpy(verts_trgt).to(dev)
-    dist1, _ = nn_distances(p, g)  # for every GT point its nearest prediction (eval_mesh.py:88)
+    if exact_recall:  # for every GT point the predicted surface itself
+        dist1 = mesh_distances(apply_transform(m_verts, sfm_to_gt), m_faces, g, box=scene_config[bbx_name])[0]
+    else:
+        dist1, _ = nn_distances(p, g)  # for every GT point its nearest prediction (eval_mesh.py:88)
     dist2, _ = nn_distances(g, p)  # for every predicted point its nearest GT point (:89)
 
     thresholds = list(threshold) if isinstance(threshold, (list, tuple, np.ndarray)) else [threshold]
@@ -573,8 +791,11 @@ def eval_mesh(file_pred, file_trgt, scene_config, is_mesh, threshold=.1, bbx_nam
             os.makedirs(save_path, exist_ok=True)
             _write_error_cloud(os.path.join(save_path, "error_pred_precision.ply"), p, dist2, t)
             _write_error_cloud(os.path.join(save_path, "error_gt_recal.ply"), g, dist1, t)
+    summary = {"thresholds": [float(t) for t in thresholds], "fscores": fscores, "precs": precs, "recals": recals}
+    if exact_recall:
+        summary["recal_mode"] = "exact"
     with open(os.path.join(save_dir, "metrics.json"), "w") as fh:
-        json.dump({"thresholds": [float(t) for t in thresholds], "fscores": fscores, "precs": precs, "recals": recals}, fh)
+        json.dump(summary, fh)
     log("fscores: %s" % fscores)
     log("precs: %s" % precs)
     log("recals: %s" % recals)

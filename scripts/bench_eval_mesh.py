@@ -17,6 +17,17 @@ table: torch.rand x 3, torch.searchsorted, one gather of the faces, three gather
 to each time: the bytes it moves.  For the fused kernel that is what the algorithm needs (area table, faces and vertices
 read once, 24 bytes written per sample); for the composition it is the operand and result sizes of every torch op summed
 (`composed_bytes`).  Kernel names: surf_weights_kernel, surf_sample_kernel.
+
+Point-to-mesh row (`point_to_mesh` in the JSON line; --ptm_queries 0 skips it): the exact recall side (evalmesh.TriGrid,
+csrc/ncw_ptm.hip) -- --ptm_queries points (1 M) near the surface against the lat-long mesh with --ptm_faces triangles (2 M),
+float64: grid build (pack, count, prefix sum, emit, sort, cell table) and query (query keys, sort, large list + shell
+search, escape pass) timed separately, with the grid's `pairs`, `large` and `escaped`.  Beside it, in the same call, the
+path it replaces, composed from the functions that exist: `sample_surface` of --ptm_samples points (10 M) from the same
+mesh, then `recentre` + `NNGrid` over the samples, then `query` of the same points (`sampled_recall`).  `mean_dist_*`: the
+mean distance each path reports (the sampled one is the larger: its bias).  `query_ms_off_poles`: the exact query over the
+queries more than 26 degrees from the poles only -- the lat-long mesh leaves a hole at each pole and crowds needle triangles
+around it, so the few queries there walk several shells of full cells and set the launch's tail.  Kernel names: ptm_pack_kernel, ptm_count_kernel,
+ptm_emit_kernel, ptm_ranges_kernel, ptm_cell_keys_kernel, ptm_query_kernel, ptm_brute_kernel, ptm_brute_finish_kernel.
 """
 import argparse
 import json
@@ -123,6 +134,41 @@ def bench_surface(args, dev, res):
     res["surface_sampling"] = out
 
 
+def bench_ptm(args, dev, res):
+    v, f = sphere_mesh(args.ptm_faces, dev)
+    q = torch.from_numpy(surface(args.ptm_queries, 3)).to(dev)
+    out = {"n_queries": int(q.shape[0]), "n_faces": int(f.shape[0]), "n_verts": int(v.shape[0])}
+    centre, cmax = evalmesh.ptm_centre(v, q)
+    grid, out["build_ms"] = timed(lambda: evalmesh.TriGrid(v, f, centre, cmax), args.reps)
+    (d_exact, _), out["query_ms"] = timed(lambda: grid.query(q), args.reps)
+    st = {}
+    grid.query(q, stats=st)
+    out.update(grid_dims=st["dims"], cell_m=grid.h, pairs=st["pairs"], large=st["large"], escaped=st["escaped"],
+               total_ms=out["build_ms"] + out["query_ms"], mean_dist_exact_m=float(d_exact.mean()))
+    dirs = q - torch.tensor([500.0, -300.0, 40.0], dtype=torch.float64, device=dev)
+    q_off = q[(dirs[:, 2].abs() < 0.9 * dirs.norm(dim=1))].contiguous()
+    _, out["query_ms_off_poles"] = timed(lambda: grid.query(q_off), args.reps)
+    out["n_queries_off_poles"] = int(q_off.shape[0])
+    # the sampled recall this replaces: sample_surface -> NNGrid -> query
+    samp = {"n_samples": args.ptm_samples}
+    pts, samp["sample_ms"] = timed(lambda: evalmesh.sample_surface(v, f, args.ptm_samples, seed=0), args.reps)
+
+    def build():
+        r32, q32, c, _ = evalmesh.recentre(pts, q)
+        return evalmesh.NNGrid(r32, c), q32
+
+    (nn, q32), samp["grid_build_ms"] = timed(build, args.reps)
+    (d_samp, _), samp["query_ms"] = timed(lambda: nn.query(q32), args.reps)
+    st = {}
+    nn.query(q32, st)
+    samp.update(grid_dims=nn.dims, escaped=st["escaped"], total_ms=samp["sample_ms"] + samp["grid_build_ms"] + samp["query_ms"],
+                mean_dist_sampled_m=float(d_samp.double().mean()))
+    out["sampled_recall"] = samp
+    out["exact_over_sampled_total"] = out["total_ms"] / samp["total_ms"]
+    out["max_exact_minus_sampled_m"] = float((d_exact - d_samp.double()).max())
+    res["point_to_mesh"] = out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--n_query", type=int, default=1_000_000)
@@ -132,6 +178,9 @@ def main():
     ap.add_argument("--no_cpu", action="store_true", help="skip the scipy cKDTree comparison")
     ap.add_argument("--surf_samples", type=int, default=10_000_000, help="surface sampling row: samples (0 = skip the row)")
     ap.add_argument("--surf_faces", type=int, default=2_000_000, help="surface sampling row: triangles of the mesh")
+    ap.add_argument("--ptm_queries", type=int, default=1_000_000, help="point-to-mesh row: queries (0 = skip the row)")
+    ap.add_argument("--ptm_faces", type=int, default=2_000_000, help="point-to-mesh row: triangles of the mesh")
+    ap.add_argument("--ptm_samples", type=int, default=10_000_000, help="point-to-mesh row: samples of the sampled path beside it")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     P = surface(args.n_ref, 1)
@@ -168,6 +217,8 @@ def main():
             res["max_abs_diff_vs_ckdtree"] = float(np.max(np.abs(d_qp.double().cpu().numpy() - dk)))
     if args.surf_samples > 0:
         bench_surface(args, dev, res)
+    if args.ptm_queries > 0:
+        bench_ptm(args, dev, res)
     print(json.dumps(res))
 
 

@@ -13,6 +13,9 @@ ground-truth cloud, nearest neighbours on the GPU (neuralrecon_w_amd.evalmesh).
   * --sample_surface [K] (K = 10 when omitted, the reference's value) scores a predicted MESH by its surface, as the
     reference's open3d branch does with --mesh: K |GT| points drawn uniformly by area on the GPU from the triangles inside
     the box (--surface_seed, --surface_mode iid|stratified);
+  * --exact_recall measures the recall side (GT point -> prediction) to the predicted SURFACE: exact point-to-triangle
+    distances on the GPU instead of the distance to the nearest vertex or sample; the prediction must have faces; the
+    precision side is unchanged; metrics.json gains "recal_mode": "exact";
   * --error_clouds also writes visualize/<t>/error_pred_precision.ply and error_gt_recal.ply (jet colours of the errors).
 """
 import argparse
@@ -45,6 +48,8 @@ def get_opts(argv=None):
     ap.add_argument("--surface_mode", choices=["iid", "stratified"], default="stratified", help="how the samples are drawn")
     ap.add_argument("--error_clouds", default=False, action="store_true",
                     help="write the error-coloured clouds of every threshold")
+    ap.add_argument("--exact_recall", default=False, action="store_true",
+                    help="recall from exact point-to-triangle distances to the predicted mesh (needs faces)")
     return ap.parse_args(argv)
 
 
@@ -63,7 +68,8 @@ def main(argv=None):
                "voxel_size": args.voxel_size}
     evalmesh.eval_mesh(args.file_pred, args.file_trgt, scene_config, args.mesh, threshold=thresholds, bbx_name=args.bbx_name,
                        save_name=args.save_name, sfm=sfm, surface=args.sample_surface, surface_seed=args.surface_seed,
-                       surface_mode=args.surface_mode, error_clouds=True if args.error_clouds else None)
+                       surface_mode=args.surface_mode, error_clouds=True if args.error_clouds else None,
+                       exact_recall=args.exact_recall)
 
 
 if __name__ == "__main__":

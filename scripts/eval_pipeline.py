@@ -11,7 +11,9 @@ Reads <pred_dir>/mesh/extracted_mesh_level_10_colored.ply, <data_root>/<scene>/{
 already in GT coordinates: the two steps chain correctly only when sfm2gt is the identity.
 
 --sample_surface / --surface_seed / --surface_mode / --error_clouds are handed to eval_mesh as scripts/eval_mesh.py does.
-The file the pipeline scores, reprojected.ply, is a point cloud: --sample_surface needs faces and is refused on it.
+The file the pipeline scores, reprojected.ply, is a point cloud: --sample_surface needs faces and is refused on it, and so
+is --exact_recall (exact point-to-triangle recall, scripts/eval_mesh.py), before any work: the reprojection filter does not
+keep the faces.
 """
 import argparse
 import os
@@ -32,11 +34,17 @@ def parse_args(argv=None):
     ap.add_argument("--surface_mode", choices=["iid", "stratified"], default="stratified", help="how the samples are drawn")
     ap.add_argument("--error_clouds", default=False, action="store_true",
                     help="write the error-coloured clouds of every threshold")
+    ap.add_argument("--exact_recall", default=False, action="store_true",
+                    help="refused here: reprojected.ply has no faces (score a mesh with scripts/eval_mesh.py --exact_recall)")
     return ap.parse_args(argv)
 
 
 def main(argv=None):
     args = parse_args(argv)
+    if args.exact_recall:
+        raise SystemExit("--exact_recall needs a triangle mesh: the pipeline scores mesh/reprojected.ply, a point cloud (the "
+                         "reprojection filter does not keep the faces).  Score the mesh itself with scripts/eval_mesh.py "
+                         "--exact_recall.")
     print("Evaluating %s ..." % args.pred_dir)
     reproj.eval_pipeline(args.scene_name, args.pred_dir, args.data_root, surface=args.sample_surface,
                          surface_seed=args.surface_seed, surface_mode=args.surface_mode,
