@@ -558,6 +558,8 @@ typedef struct NcwCompositeGrad {
                         * per-point adjoints the MLP backward kernels round to fp16 stay in its normal range; the caller
                         * divides it back out of the parameter gradients (NcwUnpackDesc.scale), d_a and d_inv_s */
     const float* grad_scale_dev; /* device scalar multiplied on top of grad_scale (the dynamic loss scale) or NULL */
+    const float* d_normals;      /* [R,3] upstream or NULL: cotangent of NcwCompositeOut.normals (the floor-normal loss);
+                                  * NULL runs the kernel without its two terms (the same program as before the field existed) */
 } NcwCompositeGrad;
 
 /* Dead-background elimination (renderer.py:637,693-708 with trim_sphere): the background NeRF's density / colour in
@@ -588,6 +590,21 @@ int ncw_ray_tail_bwd(const float* weights_sum, const int64_t* label, const int* 
                      const float* scalars, const float* d_mask_error, const float* d_sfm_depth_loss,
                      const float* d_gradient_error, float* d_weights_sum, float* d_depth, float* d_eik_num,
                      void* stream);
+
+/* The floor-normal term of render() (renderer.py:918-945 floor_loss) and its backward.  floor[r] = label[r] (int64) is one of
+ * floor_ids (HOST, <= 4 ids); n_gt (HOST): the unit floor normal in SfM coordinates.
+ *   floor_error[r,:] = |normals[r,:] - n_gt| * floor[r] * (scaled ? R / max(n_floor, 1) : 1)       [R,3]
+ *   scalars: DEVICE float[2] = {n_floor, y_var}; y_var = unbiased variance over the 3 n_floor coordinates of
+ *            rays_o + rays_d * depth on the floor rays (0 when there is none)
+ * scaled = 1 is the sync-free form: the mean over all R rows equals the reference's mean over the floor rows.
+ * One workgroup, order-fixed sums (no atomics): bitwise reproducible. */
+int ncw_ray_floor_fwd(const float* normals, const int64_t* label, const int* floor_ids, int n_ids, const float n_gt[3],
+                      const float* rays_o, const float* rays_d, const float* depth, int R, int scaled,
+                      float* floor_error /*[R,3]*/, float* scalars /*[2]*/, void* stream);
+/* d_normals [R,3] = d_floor_error * sign(normals - n_gt) * floor * scale, sign(0) = 0; scalars as written by the forward */
+int ncw_ray_floor_bwd(const float* normals, const int64_t* label, const int* floor_ids, int n_ids, const float n_gt[3],
+                      int R, int scaled, const float* scalars, const float* d_floor_error /*[R,3]*/,
+                      float* d_normals /*[R,3]*/, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Iso-surface extraction: replaces `skimage.measure.marching_cubes(sdf, level, mask=...)` of

@@ -12,6 +12,7 @@
 //   ncw_ray_sum_rows, ncw_scatter_add_rows   per-ray sum / embedding scatter of the appearance-code adjoints
 //   ncw_batch_assemble                       a training batch gathered from the HBM-resident ray cache
 //   ncw_ray_tail_fwd / _bwd                  the per-ray loss terms render() returns
+//   ncw_ray_floor_fwd / _bwd                 the floor-normal term of render() (renderer.py:918-945)
 //   ncw_bg_select                            which samples need the background NeRF at all
 #include "../../include/neuconw_hip.h"
 #include "ncw_common.h"
@@ -482,7 +483,9 @@ NCW_DEV void wave_suffix_excl_sum(const float* a, float* out, int m, int lane) {
     __builtin_amdgcn_wave_barrier();
 }
 
-template <int MAXN>
+// NRM: G.d_normals is given (the floor-normal loss reads the rendered normal sum_{j<S} grad_j w_j): two more terms, compiled
+// in only then -- without it this is the kernel as it was.
+template <int MAXN, bool NRM>
 __global__ __launch_bounds__(256) void composite_bwd_kernel(NcwCompositeIn A, NcwCompositeGrad G) {
     constexpr int CH = MAXN / 64;
     __shared__ float sm[4][5][MAXN];
@@ -504,6 +507,10 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(NcwCompositeIn A, Nc
     if (A.background_rgb)
         dws -= dcr * A.background_rgb[0] + dcg * A.background_rgb[1] + dcb * A.background_rgb[2];
     const float ddep = G.d_depth[r] * gs, deik = G.d_eik_num[r] * gs;
+    float dnx = 0.f, dny = 0.f, dnz = 0.f;
+    if constexpr (NRM) {
+        dnx = G.d_normals[r * 3] * gs; dny = G.d_normals[r * 3 + 1] * gs; dnz = G.d_normals[r * 3 + 2] * gs;
+    }
     // recompute alpha0, bg alpha
     for (int i = lane; i < S; i += 64) {
         const size_t q = (size_t)r * S + i;
@@ -549,7 +556,16 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(NcwCompositeIn A, Nc
             const size_t q = ((size_t)r * M + j) * 3;
             rr = A.bg_rgb[q]; gg = A.bg_rgb[q + 1]; bb = A.bg_rgb[q + 2];
         } else rr = gg = bb = 0.f;
-        wbar[j] = dcr * rr + dcg * gg + dcb * bb + (ins ? dws : 0.f);
+        float wb = dcr * rr + dcg * gg + dcb * bb + (ins ? dws : 0.f);
+        if constexpr (NRM) {
+            // normals take grad_j w_j of EVERY primary sample, inside the sphere or not (the merged weight): outside it
+            // the alpha is the background's, so this part of dalpha leaves through d_density below
+            if (j < S) {
+                const size_t q = ((size_t)r * S + j) * 3;
+                wb += dnx * A.grad[q] + dny * A.grad[q + 1] + dnz * A.grad[q + 2];  // re-read, not kept: no LDS row left for it
+            }
+        }
+        wbar[j] = wb;
     }
     __builtin_amdgcn_wave_barrier();
     wave_excl_scan<true, CH>(T, T, M, lane);
@@ -602,9 +618,16 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(NcwCompositeIn A, Nc
         const float gn = sqrtf(gx * gx + gy * gy + gz * gz);
         const float ek = (gn > 0.f) ? deik * relax * 2.0f * (gn - 1.0f) / gn : 0.f;
         G.d_sdf[q] = dep + dne;
-        G.d_grad[q * 3] = dtc * y.dx + ek * gx;
-        G.d_grad[q * 3 + 1] = dtc * y.dy + ek * gy;
-        G.d_grad[q * 3 + 2] = dtc * y.dz + ek * gz;
+        if constexpr (NRM) {
+            const float w = alm[i] * T[i];  // still the merged alpha and transmittance of chain A
+            G.d_grad[q * 3] = dtc * y.dx + ek * gx + w * dnx;
+            G.d_grad[q * 3 + 1] = dtc * y.dy + ek * gy + w * dny;
+            G.d_grad[q * 3 + 2] = dtc * y.dz + ek * gz + w * dnz;
+        } else {
+            G.d_grad[q * 3] = dtc * y.dx + ek * gx;
+            G.d_grad[q * 3 + 1] = dtc * y.dy + ek * gy;
+            G.d_grad[q * 3 + 2] = dtc * y.dz + ek * gz;
+        }
     }
     ds_acc = wave_sum(ds_acc);
     if (lane == 0) G.d_inv_s[r] = ds_acc;  // per-ray term; the caller sums them (no atomics: reproducible)
@@ -678,7 +701,9 @@ extern "C" int ncw_composite_bwd(const NcwCompositeIn* in, const NcwCompositeGra
     if (in->S < 1 || !cap) return NCW_E_BADARG;
     NcwCompositeGrad G = *g;
     if (G.grad_scale == 0.f) G.grad_scale = 1.0f;
-    hipLaunchKernelGGL(cap == RAY_CAP_SMALL ? composite_bwd_kernel<RAY_CAP_SMALL> : composite_bwd_kernel<RAY_CAP_LARGE>, dim3((in->R + 3) / 4), dim3(256), 0, (hipStream_t)stream, *in, G);
+    auto kernel = cap == RAY_CAP_SMALL ? composite_bwd_kernel<RAY_CAP_SMALL, false> : composite_bwd_kernel<RAY_CAP_LARGE, false>;
+    if (G.d_normals) kernel = cap == RAY_CAP_SMALL ? composite_bwd_kernel<RAY_CAP_SMALL, true> : composite_bwd_kernel<RAY_CAP_LARGE, true>;
+    hipLaunchKernelGGL(kernel, dim3((in->R + 3) / 4), dim3(256), 0, (hipStream_t)stream, *in, G);
     NCW_CHECK_LAUNCH();
     return 0;
 }
@@ -922,6 +947,107 @@ extern "C" int ncw_ray_tail_bwd(const float* weights_sum, const int64_t* label, 
     return 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Floor-normal term of render() (renderer.py:918-945 floor_loss) and its backward.  floor[r] = label[r] is one of ids;
+//   floor_error[r,:] = |normals[r,:] - n_gt| floor[r] (scaled ? R / max(n_floor, 1) : 1)
+//   scalars = {n_floor, y_var},  y_var = torch.var (unbiased) of the 3 n_floor coordinates of rays_o + rays_d depth on the
+//             floor rays (two passes in double: a mean, then the squared deviations), 0 if there is none
+// One workgroup and fixed-order sums like ray_tail_fwd_kernel: run-to-run identical.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ double block_sum256d(double v, double* sm) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return sm[0] + sm[1] + sm[2] + sm[3];
+}
+
+struct FloorGt { float v[3]; };
+
+__global__ __launch_bounds__(256) void ray_floor_fwd_kernel(const float* __restrict__ normals, const int64_t* __restrict__ label,
+                                                            const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                                                            const float* __restrict__ depth, int R, int n_ids, TailIds ids,
+                                                            FloorGt gt, int scaled, float* __restrict__ floor_error,
+                                                            float* __restrict__ scal) {
+    __shared__ double sm[4];
+    double cnt = 0.0, sum = 0.0;
+    for (int r = threadIdx.x; r < R; r += 256) {
+        if (tail_mask(label, r, n_ids, ids.v) != 0.f) continue;  // mask 0 = the label is one of ids
+        const double t = depth[r];
+        cnt += 1.0;
+        for (int k = 0; k < 3; ++k) sum += (double)rays_o[r * 3 + k] + (double)rays_d[r * 3 + k] * t;
+    }
+    cnt = block_sum256d(cnt, sm);
+    sum = block_sum256d(sum, sm);
+    const double mean = cnt > 0.0 ? sum / (3.0 * cnt) : 0.0;
+    double dev = 0.0;
+    for (int r = threadIdx.x; r < R; r += 256) {
+        if (tail_mask(label, r, n_ids, ids.v) != 0.f) continue;
+        const double t = depth[r];
+        for (int k = 0; k < 3; ++k) {
+            const double e = (double)rays_o[r * 3 + k] + (double)rays_d[r * 3 + k] * t - mean;
+            dev += e * e;
+        }
+    }
+    dev = block_sum256d(dev, sm);
+    if (threadIdx.x == 0) {
+        scal[0] = (float)cnt;
+        scal[1] = cnt > 0.0 ? (float)(dev / (3.0 * cnt - 1.0)) : 0.f;
+    }
+    const float rs = scaled ? (float)R / fmaxf((float)cnt, 1.f) : 1.f;
+    for (int r = threadIdx.x; r < R; r += 256) {
+        const float f = (1.f - tail_mask(label, r, n_ids, ids.v)) * rs;
+        for (int k = 0; k < 3; ++k) floor_error[r * 3 + k] = fabsf(normals[r * 3 + k] - gt.v[k]) * f;
+    }
+}
+
+__global__ __launch_bounds__(256) void ray_floor_bwd_kernel(const float* __restrict__ normals, const int64_t* __restrict__ label,
+                                                            int R, int n_ids, TailIds ids, FloorGt gt, int scaled,
+                                                            const float* __restrict__ scal, const float* __restrict__ d_fe,
+                                                            float* __restrict__ d_normals) {
+    const float rs = scaled ? (float)R / fmaxf(scal[0], 1.f) : 1.f;
+    for (int r = blockIdx.x * 256 + threadIdx.x; r < R; r += gridDim.x * 256) {
+        const float f = (1.f - tail_mask(label, r, n_ids, ids.v)) * rs;
+        for (int k = 0; k < 3; ++k) {
+            const float e = normals[r * 3 + k] - gt.v[k];
+            const float sg = e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f);  // torch's L1: sign(0) = 0
+            d_normals[r * 3 + k] = d_fe[r * 3 + k] * sg * f;
+        }
+    }
+}
+
+extern "C" int ncw_ray_floor_fwd(const float* normals, const int64_t* label, const int* floor_ids, int n_ids,
+                                 const float n_gt[3], const float* rays_o, const float* rays_d, const float* depth, int R,
+                                 int scaled, float* floor_error, float* scalars, void* stream) {
+    if (R <= 0) return 0;
+    if (!normals || !label || !n_gt || !rays_o || !rays_d || !depth || !floor_error || !scalars || n_ids < 0 || n_ids > 4 ||
+        (n_ids > 0 && !floor_ids))
+        return NCW_E_BADARG;
+    TailIds ids = {{0, 0, 0, 0}};
+    for (int i = 0; i < n_ids; ++i) ids.v[i] = floor_ids[i];
+    const FloorGt gt = {{n_gt[0], n_gt[1], n_gt[2]}};
+    hipLaunchKernelGGL(ray_floor_fwd_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, normals, label, rays_o, rays_d, depth, R,
+                       n_ids, ids, gt, scaled, floor_error, scalars);
+    NCW_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int ncw_ray_floor_bwd(const float* normals, const int64_t* label, const int* floor_ids, int n_ids,
+                                 const float n_gt[3], int R, int scaled, const float* scalars, const float* d_floor_error,
+                                 float* d_normals, void* stream) {
+    if (R <= 0) return 0;
+    if (!normals || !label || !n_gt || !scalars || !d_floor_error || !d_normals || n_ids < 0 || n_ids > 4 ||
+        (n_ids > 0 && !floor_ids))
+        return NCW_E_BADARG;
+    TailIds ids = {{0, 0, 0, 0}};
+    for (int i = 0; i < n_ids; ++i) ids.v[i] = floor_ids[i];
+    const FloorGt gt = {{n_gt[0], n_gt[1], n_gt[2]}};
+    hipLaunchKernelGGL(ray_floor_bwd_kernel, dim3((R + 255) / 256), dim3(256), 0, (hipStream_t)stream, normals, label, R, n_ids,
+                       ids, gt, scaled, scalars, d_floor_error, d_normals);
+    NCW_CHECK_LAUNCH();
+    return 0;
+}
 
 // ------------------------------------------------------------------------------------------------
 // Dead-background elimination: which ray samples need the background NeRF at all (include/neuconw_hip.h, ncw_bg_select).

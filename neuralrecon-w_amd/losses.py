@@ -2,10 +2,15 @@
 instead of the ~25 tiny torch kernels of sub / abs / sum / div / mean x3 / mul / add and their autograd backward.
 
     loss = coef * ( sum|color - rgbs| / (R + 1e-5)  +  igr_weight * gradient_error
-                    + [MESH_MASK_LIST] mask_weight * mean(mask_error)  +  [DEPTH_LOSS] depth_weight * mean(sfm_depth_loss) )
+                    + [MESH_MASK_LIST] mask_weight * mean(mask_error)  +  [DEPTH_LOSS] depth_weight * mean(sfm_depth_loss)
+                    + [FLOOR_NORMAL] depth_weight * mean(floor_normal_error) )
+
+The floor term's weight IS depth_weight: the reference's constructor stores `self.floor_weight = depth_weight` (losses.py:17)
+and never reads its `floor_weight` argument; reproduced on purpose, the argument is accepted and ignored here too.  The term is
+added in torch on top of the fused launch (a mean and an add each way).
 
 The reference returns the terms as a dict and `training_step` sums them (neuconw_system.py:355-357); `__call__` here
-returns that sum, `terms()` the dict (plain torch, for logging).  `floor_normal` is not on the HIP path (renderer refuses it)."""
+returns that sum, `terms()` the dict (plain torch, for logging)."""
 import torch
 
 from . import lib as L
@@ -51,13 +56,15 @@ class NeuconWLoss:
     config dict (neuralrecon_w_amd.config) or None (then `use_mask` / `use_depth` decide which terms exist)."""
 
     def __init__(self, coef=1, igr_weight=0.1, mask_weight=0.1, depth_weight=0.1, floor_weight=0.01, config=None,
-                 use_mask=True, use_depth=True):
+                 use_mask=True, use_depth=True, use_floor=False):
         self.coef, self.igr_weight, self.mask_weight, self.depth_weight = float(coef), float(igr_weight), float(mask_weight), float(depth_weight)
         if config is not None:
             n = config["NEUCONW"] if isinstance(config, dict) else config.NEUCONW
             get = (lambda k: n[k]) if isinstance(n, dict) else (lambda k: getattr(n, k))
             use_mask, use_depth = get("MESH_MASK_LIST") is not None, bool(get("DEPTH_LOSS"))
-        self.use_mask, self.use_depth = bool(use_mask), bool(use_depth)
+            use_floor = bool(get("FLOOR_NORMAL"))
+        self.use_mask, self.use_depth, self.use_floor = bool(use_mask), bool(use_depth), bool(use_floor)
+        self.floor_weight = self.depth_weight  # losses.py:17; `floor_weight` (the argument) is ignored, as there
 
     def __call__(self, inputs, targets):
         if not inputs["color"].is_cuda:
@@ -66,8 +73,11 @@ class NeuconWLoss:
         ge = inputs["gradient_error"]
         if ge.numel() != 1:  # losses.py:29 takes .mean(); render() returns the batch-global scalar (renderer.py:763-765),
             ge = ge.mean()   # any other shape is reduced here by torch (with its autograd) before the fused launch
-        return _LossFn.apply(inputs["color"], targets, ge, inputs["mask_error"] if self.use_mask else None,
+        loss = _LossFn.apply(inputs["color"], targets, ge, inputs["mask_error"] if self.use_mask else None,
                              inputs["sfm_depth_loss"] if self.use_depth else None, w)
+        if self.use_floor:
+            loss = loss + (self.coef * self.floor_weight) * inputs["floor_normal_error"].mean()
+        return loss
 
     def terms(self, inputs, targets):
         """The reference's return value (a dict of weighted terms), in plain torch."""
@@ -78,4 +88,6 @@ class NeuconWLoss:
             ret["mask_error"] = self.mask_weight * inputs["mask_error"].mean()
         if self.use_depth:
             ret["sfm_depth_loss"] = self.depth_weight * inputs["sfm_depth_loss"].mean()
+        if self.use_floor:
+            ret["floor_normal_error"] = self.floor_weight * inputs["floor_normal_error"].mean()
         return {k: self.coef * v for k, v in ret.items()}

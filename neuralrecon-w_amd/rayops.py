@@ -111,11 +111,16 @@ class CompositeCtx:
         L.check(lib.ncw_composite_fwd(self.cin, s, L.stream_ptr(dev)), "ncw_composite_fwd")
         return o
 
-    def backward(self, d_color, d_weights_sum, d_depth, d_eik_num, grad_scale=1.0, grad_scale_dev=None):
+    def backward(self, d_color, d_weights_sum, d_depth, d_eik_num, grad_scale=1.0, grad_scale_dev=None, d_normals=None):
+        """d_normals [R,3]: cotangent of the forward's `normals` (the floor-normal loss); None leaves its terms out of the
+        kernel altogether (another instantiation), it is not a zero buffer."""
         R, S, M, dev = self.R, self.S, self.S + self.O, self.dev
         z = lambda t, shape: _f(t).reshape(shape) if t is not None else torch.zeros(shape, device=dev)  # noqa: E731
         ups = dict(d_color=z(d_color, (R, 3)), d_weights_sum=z(d_weights_sum, (R,)), d_depth=z(d_depth, (R,)),
                    d_eik_num=z(d_eik_num, (R,)))
+        if d_normals is not None:
+            _chk_cuda(d_normals)
+            ups["d_normals"] = _f(d_normals).reshape(R, 3)
         g = dict(d_sdf=torch.empty(R, S, device=dev), d_grad=torch.empty(R, S, 3, device=dev),
                  d_rgb=torch.empty(R, S, 3, device=dev),
                  d_density=torch.empty(R, M, device=dev) if self.has_bg else None,

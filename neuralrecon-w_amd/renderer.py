@@ -3,7 +3,7 @@ keywords, same `render()` output dictionary, same helper methods (`sdf`, `rgb`, 
 mutable attributes -- the body runs the hand-written gfx950 kernels of libneuconw_hip.so.
 
 Only per-RAY glue (ray normalisation, the embedding lookup) stays in torch; the per-ray loss terms render()
-returns (gradient_error, mask_error, sfm_depth_loss) are one C-ABI launch (`_RayTailFn`); everything per ray-SAMPLE (sampling, the three MLPs forward and backward,
+returns (gradient_error, mask_error, sfm_depth_loss) are one C-ABI launch (`_RayTailFn`), the floor-normal term another (`_RayFloorFn`); everything per ray-SAMPLE (sampling, the three MLPs forward and backward,
 compositing) is HIP.  Autograd sees ONE node (`_RenderFn`) whose backward launches the fused
 backward kernels and returns the gradients of every parameter.
 """
@@ -104,7 +104,9 @@ class _RenderFn(torch.autograd.Function):
         extras = (o["color_sphere"], o["color_bg"], o["weights"], o["cdf"], o["inside"], o["normals"],
                   sdf.view(R, S), grad.view(R, S, 3), o["mid_z"], o["dists"], o["eik"][1], inv_s, s_val,
                   o["weights_max"])
-        ctx.mark_non_differentiable(*extras)
+        # normals is differentiable only for the floor-normal loss (its cotangent goes to the compositor backward)
+        ctx.floor_normal = bool(rdr.floor_normal)
+        ctx.mark_non_differentiable(*((extras[:5] + extras[6:]) if ctx.floor_normal else extras))  # extras[5]: normals
         # the leases live exactly as long as this autograd node: returned by backward(), or when the node is dropped
         ctx.guard = LeaseGuard([c["lease"] for c in (sctx, cctx, nctx) if c is not None])
         ctx.train = train
@@ -130,7 +132,10 @@ class _RenderFn(torch.autograd.Function):
         # overflowed step and grow it back (trainer.FlatAdam / ncw_adam_step_dev) without a device->host round trip.
         sc = rdr.loss_scale.tensor(dev) if prec == L.PREC_F16 else None
         sc_mul, sc_inv = (sc[0:1], sc[1:2]) if sc is not None else (None, None)
-        g = comp.backward(d_color, d_wsum, d_depth, d_eik, grad_scale_dev=sc_mul)
+        if ctx.floor_normal:  # unused[5]: normals (None when no floor ray took part: then the launch is the option-off one)
+            g = comp.backward(d_color, d_wsum, d_depth, d_eik, grad_scale_dev=sc_mul, d_normals=unused[5])
+        else:
+            g = comp.backward(d_color, d_wsum, d_depth, d_eik, grad_scale_dev=sc_mul)
         R, S = comp.R, comp.S
         d_grad = g["d_grad"].view(R * S, 3)
         dfeat_ptr = sctx["arena"].ptr(sctx["ids"]["dfeat"])
@@ -292,6 +297,39 @@ class _RayTailFn(torch.autograd.Function):
         return d_wsum, d_depth, d_num, None, None, None, None, None, None, None
 
 
+class _RayFloorFn(torch.autograd.Function):
+    """floor_loss of render() (renderer.py:918-945) as one forward and one backward launch (ncw_ray_floor_fwd/bwd):
+    -> floor_error [R,3] (dense; `scaled`: times R / max(n_floor, 1)) and scalars {n_floor, y_var} (not differentiable)."""
+
+    @staticmethod
+    def forward(ctx, normals, label, rays_o, rays_d, depth, ids, n_gt, scaled):
+        R, dev = normals.shape[0], normals.device
+        f = lambda t: t.detach().contiguous().float()  # noqa: E731
+        normals_c, label_c = f(normals), label.contiguous().long()
+        fe, scal = torch.empty(R, 3, device=dev), torch.zeros(2, device=dev)
+        ids_arr = (C.c_int * 4)(*(list(ids) + [0] * (4 - len(ids))))
+        gt_arr = (C.c_float * 3)(*n_gt)
+        L.check(L.get_lib().ncw_ray_floor_fwd(L.ptr(normals_c), L.ptr(label_c), ids_arr, len(ids), gt_arr, L.ptr(f(rays_o)),
+                                              L.ptr(f(rays_d)), L.ptr(f(depth)), R, int(scaled), L.ptr(fe), L.ptr(scal),
+                                              L.stream_ptr(dev)), "ncw_ray_floor_fwd")
+        ctx.keep = (normals_c, label_c, ids_arr, len(ids), gt_arr, int(scaled), scal)
+        ctx.mark_non_differentiable(scal)
+        ctx.set_materialize_grads(False)
+        return fe, scal
+
+    @staticmethod
+    def backward(ctx, d_fe, _d_scal):
+        normals_c, label_c, ids_arr, n_ids, gt_arr, scaled, scal = ctx.keep
+        if d_fe is None:
+            return (None,) * 8
+        R, dev = normals_c.shape[0], normals_c.device
+        d_fe = d_fe.contiguous().float()
+        d_normals = torch.empty(R, 3, device=dev)
+        L.check(L.get_lib().ncw_ray_floor_bwd(L.ptr(normals_c), L.ptr(label_c), ids_arr, n_ids, gt_arr, R, scaled, L.ptr(scal),
+                                              L.ptr(d_fe), L.ptr(d_normals), L.stream_ptr(dev)), "ncw_ray_floor_bwd")
+        return (d_normals,) + (None,) * 7
+
+
 class LossScale:
     """The fp16 mode's loss scale as device data: float[2] = {scale, 1 / scale} (powers of two).  The compositor backward
     multiplies its upstream cotangents by [0] (NcwCompositeGrad.grad_scale_dev), the weight-norm backward / d_a / d_var
@@ -353,8 +391,9 @@ class NeuconWRenderer:
         self.depth_loss, self.save_sample, self.trim_sphere = depth_loss, save_sample, trim_sphere
         self.mesh_mask_list = mesh_mask_list
         self.save_step_sample = save_step_sample
-        if floor_normal:
-            raise NotImplementedError("floor_normal loss is not on the HIP path (all scene yamls ship FLOOR_NORMAL: False)")
+        if floor_normal:  # the names are resolved here so that an unknown one fails now, not in the first render()
+            if len([_label_id(name) for name in (floor_labels or [])]) > 4:
+                raise ValueError("floor_labels: at most 4 labels (ncw_ray_floor_fwd), got %d" % len(floor_labels))
         if save_sample or save_step_sample:
             raise NotImplementedError("debug PLY dumps (open3d) are out of scope")
         self.prec = default_prec() if prec is None else prec
@@ -476,6 +515,16 @@ class NeuconWRenderer:
         v_far = torch.where(miss, far, (surf + rng) / self.radius)
         return v_near, v_far, ~miss
 
+    def _floor_normal_gt(self):
+        """renderer.py:930-937: e_z of the ground-truth frame in SfM coordinates, sfm_to_gt[:3,:3].T @ e_z over its float32 norm,
+        computed once per sfm_to_gt tensor on the host (3 python floats)."""
+        c = self.__dict__.get("_floor_gt")
+        if c is None or c[1] is not self.sfm_to_gt:
+            v = self.sfm_to_gt.detach().cpu().float()[:3, :3].T @ torch.tensor([0.0, 0.0, 1.0])
+            v = v / torch.linalg.norm(v)
+            self._floor_gt = c = (tuple(float(x) for x in v), self.sfm_to_gt)
+        return c[0]
+
     def _grad_views(self, params):
         key = tuple(id(p) for p in params)
         c = self.__dict__.get("_gv")
@@ -593,12 +642,31 @@ class NeuconWRenderer:
             sfm_depth_loss = (((depth - depth_gt) ** 2) * depth_weight)[depth_weight > 0]
         else:
             sfm_depth_loss = torch.zeros_like(depth)
+        # floor_loss (renderer.py:881-889, 918-945): one launch over all rays.  Default mode: the reference's shapes -- the floor
+        # rows selected on the host's say (one synchronisation, like sfm_depth_loss above), zeros [R,3] when there is none.
+        # Sync-free: the dense rows scaled by R / n_floor, whose mean is the reference's mean over the floor rows; floor_y_error
+        # then holds y_var in every entry (same mean).  floor_y_error is detached: the reference's loss never reads it.
+        floor_normal_error = floor_y_error = None
+        if self.floor_normal and label is not None:
+            fids = tuple(_label_id(name) for name in (self.floor_labels or []))
+            fe, fscal = _RayFloorFn.apply(normals, label, rays_o, rays_d, depth, fids, self._floor_normal_gt(), bool(self.sync_free))
+            if self.sync_free:
+                floor_normal_error, floor_y_error = fe, fscal[1].expand(R, 3)
+            else:
+                fmask = torch.zeros(R, dtype=torch.bool, device=device)
+                for i in fids:
+                    fmask |= label == i
+                if bool(fmask.any()):
+                    floor_normal_error = fe[fmask]
+                    floor_y_error = torch.ones_like(floor_normal_error) * fscal[1]
+        if floor_normal_error is None:
+            floor_normal_error = floor_y_error = torch.zeros_like(normals)
         return {
             "color": color, "color_sphere": color_sphere, "color_bg": color_bg, "s_val": s_val.reshape(1, 1),
             "cdf_fine": cdf, "gradients": gradients, "mask_error": mask_error, "weights": weights,
             "weights_sum": weights_sum, "weights_max": weights_max.unsqueeze(-1),
             "gradient_error": gradient_error, "inside_sphere": inside,
-            "depth": depth, "floor_normal_error": (zn := torch.zeros_like(normals)), "floor_y_error": zn,
+            "depth": depth, "floor_normal_error": floor_normal_error, "floor_y_error": floor_y_error,
             "sfm_depth_loss": sfm_depth_loss,
         }, normals
 

@@ -4,7 +4,12 @@ Shapes: the headline step (R = 1024, S = 128, O = 4, and the sampler's calls for
 the reference's defaults on the large capacity (S = 1056, O = 32, up-sampling at n = 1023).  Buffers and ABI structs are made
 once through rayops and the launches replayed through the C ABI, so a window holds kernels and not allocations.  Every shape is
 warmed up; a timed window holds at least half a second of launches and ends in a synchronise.  Prints one JSON line: us per
-launch.  Inputs are those of the per-ray tests (tests/_ray_cases.py: comp_inputs)."""
+launch.  Inputs are those of the per-ray tests (tests/_ray_cases.py: comp_inputs).
+
+--floor adds what the floor-normal loss costs: composite_bwd with a d_normals buffer (the other instantiation of the kernel) at
+both shapes, and the two launches of the floor term (ncw_ray_floor_fwd / _bwd) at R = 1024."""
+import argparse
+import ctypes
 import json
 import math
 import os
@@ -16,6 +21,10 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from neuralrecon_w_amd import lib as L  # noqa: E402
 from neuralrecon_w_amd import rayops  # noqa: E402
 from tests._ray_cases import comp_inputs  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--floor", action="store_true", help="also time composite_bwd with d_normals and the floor-term launches")
+args = ap.parse_args()
 
 R = 1024
 dev = torch.device("cuda:0")
@@ -58,7 +67,22 @@ def composite(S, O):
     grad_struct.grad_scale = 1.0
     fwd = timeit(lambda: lib.ncw_composite_fwd(ctx.cin, out_struct, st))
     bwd = timeit(lambda: lib.ncw_composite_bwd(ctx.cin, grad_struct, st))
+    if args.floor:
+        d_normals = torch.randn(R, 3, device=dev)
+        grad_struct.d_normals = d_normals.data_ptr()
+        res["composite_bwd_dn_%d+%d" % (S, O)] = timeit(lambda: lib.ncw_composite_bwd(ctx.cin, grad_struct, st))
     return I, fwd, bwd
+
+
+def floor_term(I):
+    normals, d_fe = torch.randn(R, 3, device=dev), torch.randn(R, 3, device=dev)
+    label = torch.where(torch.rand(R, device=dev) < 0.3, 6, 0)
+    depth, fe, scal, dn = torch.rand(R, device=dev) + 1.5, torch.empty(R, 3, device=dev), torch.empty(2, device=dev), torch.empty(R, 3, device=dev)
+    ids, gt = (ctypes.c_int * 4)(6, 0, 0, 0), (ctypes.c_float * 3)(0.6, 0.0, 0.8)
+    a = [L.ptr(t) for t in (normals, label, I["o"], I["d"], depth, fe, scal, d_fe, dn)]
+    fwd = timeit(lambda: lib.ncw_ray_floor_fwd(a[0], a[1], ids, 1, gt, a[2], a[3], a[4], R, 1, a[5], a[6], st))
+    bwd = timeit(lambda: lib.ncw_ray_floor_bwd(a[0], a[1], ids, 1, gt, R, 1, a[6], a[7], a[8], st))
+    return fwd, bwd
 
 
 def upsample(I, n, n_new):
@@ -86,4 +110,6 @@ I, fwd, bwd = composite(1056, 32)
 res["composite_fwd_1056+32"], res["composite_bwd_1056+32"] = fwd, bwd
 res["upsample_1023"] = upsample(I, 1023, 128)
 res["sort_merge_1056+32"] = merge(I, 1056, 32, False)
+if args.floor:
+    res["ray_floor_fwd"], res["ray_floor_bwd"] = floor_term(I)
 print(json.dumps({"unit": "us per launch, R = 1024", **{k: round(v, 3) for k, v in res.items()}}))
