@@ -50,23 +50,39 @@ NCW_DEV void ss_load_half(bf16x8 (&h)[NU], bf16x8 (&l)[NU], const void* w, const
 NCW_DEV void ss_split8(const f32x16& v, int t, bf16x8& hi, bf16x8& lo) { ncw_split8(v, t, hi, lo); }
 
 // acc[t] += W[ob, units u0 .. u0 + NU) . in[t, the same units], three MFMAs per unit; tiles in pairs so that consecutive
-// MFMAs alternate between two accumulators
+// MFMAs alternate between two accumulators.  The B fragments {hi, lo} x {tile, tile + 1} of a step (one k-unit of one tile
+// pair; the 2 NU steps of a call form ONE sequence, so the second pair's first fragments are read under the first pair's last
+// MFMAs) come from LDS through an explicit register ring, SS_RD steps ahead of their MFMAs, and the issue order is pinned
+// per step (ncw_sdf8.hip sb_mma; left to the compiler every read was followed by lgkmcnt(0) and its MFMAs, NOTEBOOK R8.1).
+// The ring is primed here, behind the barrier that published the buffer, and empty on return.  The MFMA order per
+// accumulator is what it was without the ring: results do not depend on SS_RD.
+// SS_RD: a step is 16 registers, and the burst chain holds 192 beside the ring (accumulators + two K-halves of the slice): 3 and 4
+// steps ahead spill (140 / 332 B of scratch in sdf_fwdSA); one-stream bench, sdf_fwdSA<true>: 0.696 ms at 1, 0.688 - 0.700 at 2
+constexpr int SS_RD = 2;
 template <int NU>
 NCW_DEV void ss_mma(f32x16 (&acc)[SS_TILES], const bf16x8 (&wh)[NU], const bf16x8 (&wl)[NU], const ss_lfrag* in, int upt, int u0) {
+    constexpr int NS = (SS_TILES / 2) * NU, RD = SS_RD < NS ? SS_RD : NS, R = RD + 1 < NS ? RD + 1 : NS;
+    bf16x8 b[R][4];  // {hi, lo} of tile tp, {hi, lo} of tile tp + 1
+    auto ring_read = [&](int s) {
+        const ss_lfrag* p0 = in + ((2 * (s / NU) * upt + u0 + s % NU) * 2) * 64;
+        const ss_lfrag* p1 = in + (((2 * (s / NU) + 1) * upt + u0 + s % NU) * 2) * 64;
+        b[s % R][0] = p0[0]; b[s % R][1] = p0[64];
+        b[s % R][2] = p1[0]; b[s % R][3] = p1[64];
+    };
 #pragma unroll
-    for (int tp = 0; tp < SS_TILES; tp += 2) {
+    for (int s = 0; s < RD; ++s) ring_read(s);
 #pragma unroll
-        for (int q = 0; q < NU; ++q) {
-            const ss_lfrag* p0 = in + ((tp * upt + u0 + q) * 2) * 64;
-            const ss_lfrag* p1 = in + (((tp + 1) * upt + u0 + q) * 2) * 64;
-            const bf16x8 bh0 = p0[0], bl0 = p0[64], bh1 = p1[0], bl1 = p1[64];
-            acc[tp] = NCW_MFMA_H(wh[q], bh0, acc[tp], 0, 0, 0);
-            acc[tp + 1] = NCW_MFMA_H(wh[q], bh1, acc[tp + 1], 0, 0, 0);
-            acc[tp] = NCW_MFMA_H(wl[q], bh0, acc[tp], 0, 0, 0);
-            acc[tp + 1] = NCW_MFMA_H(wl[q], bh1, acc[tp + 1], 0, 0, 0);
-            acc[tp] = NCW_MFMA_H(wh[q], bl0, acc[tp], 0, 0, 0);
-            acc[tp + 1] = NCW_MFMA_H(wh[q], bl1, acc[tp + 1], 0, 0, 0);
-        }
+    for (int s = 0; s < NS; ++s) {
+        if (s + RD < NS) ring_read(s + RD);
+        const int tp = 2 * (s / NU), q = s % NU;
+        const bf16x8 (&f)[4] = b[s % R];
+        acc[tp] = NCW_MFMA_H(wh[q], f[0], acc[tp], 0, 0, 0);
+        acc[tp + 1] = NCW_MFMA_H(wh[q], f[2], acc[tp + 1], 0, 0, 0);
+        acc[tp] = NCW_MFMA_H(wl[q], f[0], acc[tp], 0, 0, 0);
+        acc[tp + 1] = NCW_MFMA_H(wl[q], f[2], acc[tp + 1], 0, 0, 0);
+        acc[tp] = NCW_MFMA_H(wh[q], f[1], acc[tp], 0, 0, 0);
+        acc[tp + 1] = NCW_MFMA_H(wh[q], f[3], acc[tp + 1], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
     }
 }
 
@@ -139,6 +155,9 @@ NCW_DEV void ss_value_chain(const NcwSdfNet& net, const NcwPoints& src, int64_t 
         }
         ncw_lds_barrier();  // the layer output is complete
     };
+    // the NEXT hidden layer's bias fragment, requested ahead of the epilogue in front of that layer: asked for behind the
+    // barrier, the layer's first MFMA waited vmcnt(0) for it -- a whole round trip, and the drain of everything in flight
+    f32x16 bnext;
     // ---- layer 0: K = 39, the 3 gamma units ------------------------------------------------------------------
     {
         bf16x8 w0h[3], w0l[3];
@@ -149,11 +168,12 @@ NCW_DEV void ss_value_chain(const NcwSdfNet& net, const NcwPoints& src, int64_t 
         for (int t = 0; t < SS_TILES; ++t) acc[t] = bias;
         ncw_lds_barrier();  // gamma visible
         ss_mma<3>(acc, w0h, w0l, gin, 3, 0);
+        bnext = ss_bias(net.b[L - 1 > 1 ? 1 : 0], wave, lane);
         epilogue(1);
     }
     // ---- hidden layers 1 .. L-2 ------------------------------------------------------------------------------
     for (int l = 1; l < L - 1; ++l) {
-        const f32x16 bias = ss_bias(net.b[l], wave, lane) * bscale;
+        const f32x16 bias = bnext * bscale;
 #pragma unroll
         for (int t = 0; t < SS_TILES; ++t) acc[t] = bias;
         ss_load_half<8>(Bh, Bl, net.w[l], net.w_lo[l], 8, wave, 8, lane);  // second half: lands during the first
@@ -165,6 +185,7 @@ NCW_DEV void ss_value_chain(const NcwSdfNet& net, const NcwPoints& src, int64_t 
             ss_load_half<3>(wgh, wgl, net.w[l], net.w_lo[l], 8, wave, 16, lane);
             ss_mma<3>(acc, wgh, wgl, gin, 3, 0);
         }
+        bnext = ss_bias(net.b[l + 1 < L - 1 ? l + 1 : l], wave, lane);  // (one form: the last layer asks for its own again)
         epilogue(l + 1);
     }
     // ---- sdf row (1 output block), tile t by wave t ------------------------------------------------------------
@@ -460,6 +481,107 @@ NCW_DEV void sb_store_units(sb_lfrag* buf, int t, int ob, const f32x16& v, int l
     buf[(t * 16 + 2 * ob + 1) * 64 + lane] = o.f[1];
 }
 
+// d gamma_f / d x_comp of the SDF network's encoding (3 inputs, 6 octaves; sinf / cosf like the value chain's gamma):
+// freq_feature_deriv<3, 6, false> (ncw_common.h) with the point passed BY VALUE.  Given the array, the component select is
+// compiled as one indexed load from a private copy of it: 16 B of scratch per lane, the only scratch sdf_fwdSA had left.
+NCW_DEV float ss_gamma_deriv(float x0, float x1, float x2, int f, int& comp) {
+    if (f < 3) {
+        comp = f;
+        return 1.f;
+    }
+    if (f >= 3 * (2 * 6 + 1)) {
+        comp = 0;
+        return 0.f;
+    }
+    const int j = f - 3;
+    const int k = j / 6;
+    const int rem = j - k * 6;
+    const bool is_cos = rem >= 3;
+    comp = is_cos ? rem - 3 : rem;
+    const float v = comp == 2 ? x2 : (comp == 1 ? x1 : x0);
+    const float fr = (float)(1 << k);
+    const float arg = v * fr;
+    return is_cos ? -fr * sinf(arg) : fr * cosf(arg);
+}
+
+// phi'(z) = 1 - exp(-100 h) from the 16-bit post-activation h (ss_load_sprime's arithmetic on one element)
+NCW_DEV float ss_sprime(ncw_h16 h) { return 1.f - __builtin_amdgcn_exp2f((float)h * -144.26950408889634f); }
+
+// The stashed h block (tile, block rb) as it lies in memory: 8 registers of raw 16-bit, not a converted f32x16.  The adjoint
+// sweep requests it AHEAD of a tile pair's MFMAs -- and so ahead of the in-place weight reload of the layer's last pair: the
+// memory pipe returns in order, so the wait in front of the pair's epilogue is a counted vmcnt(N) that leaves the reload and
+// the previous pair's t_l stores in flight (ncw_sdf8.hip sb_mma; NOTEBOOK R8.1).
+NCW_DEV void ss_request_h(bf16x4 (&raw)[4], const ncw_h16* __restrict__ st_h, size_t tile, int RB, int rb, int lane) {
+    const bf16x4* p = reinterpret_cast<const bf16x4*>(st_h) + ((tile * RB + rb) * 4) * 64 + lane;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) raw[g] = NCW_STASH_LD(p[g * 64]);
+}
+
+// The adjoint sweep's first step, t_{L-2} = a_{L-2} * phi'(z_{L-2}) (a0: the same for every point), for this wave's block of
+// the four tiles.  phi' needs h_{L-1}, and the fp16 roundings of exactly this block -- the hi plane: the bits the stash
+// h[L-1] holds -- still lie in the split buffer where the wave wrote them in the value chain's last epilogue: they are read
+// from there, not back from HBM, BEFORE the barrier behind which the plain buffers overwrite the split one.
+template <bool TRAIN>
+NCW_DEV void ss_sweep_start(ss_lfrag* sbuf, const f32x16& a0, ncw_h16* __restrict__ st_t, size_t tile0, int wave, int lane) {
+    bf16x8 hf[SS_TILES][2];
+#pragma unroll
+    for (int t = 0; t < SS_TILES; ++t)
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) hf[t][tt] = sbuf[((t * 16 + 2 * wave + tt) * 2) * 64 + lane];
+    ncw_lds_barrier();  // every wave is done with the split buffer (feature rows, sdf row): the plain buffers alias it
+    sb_lfrag* out = (sb_lfrag*)sbuf;  // abuf0
+#pragma unroll
+    for (int t = 0; t < SS_TILES; ++t) {
+        f32x16 sv;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) sv[r] = ss_sprime(hf[t][r >> 3][r & 7]) * a0[r];
+        if (TRAIN) stash_store_block(st_t, tile0 + t, 8, wave, sv, lane);
+        sb_store_units(out, t, wave, sv, lane);
+    }
+}
+
+// The MFMA loop of the feature rows (NW = 1: acc0 / acc1 += w0[u] . B[u] of two tiles) and of the adjoint sweep (NW = 2: the hi
+// slice w0 and the lo slice w1 on every fragment, four MFMAs per k-unit) over the 16 k-units, the B fragments through a
+// register ring SA_RD units ahead (ss_mma above; in0 / in1 = the tile's first unit + lane, units STEP fragments apart).
+// RELOAD: unit u of the NEXT slice(s) (n0 / n1, fragment u * nstride + ob) replaces unit u once its MFMAs are issued -- behind
+// the fence that follows them: in one scheduling region with them the compiler hoists the load above the MFMAs that still
+// read the old registers, into fresh ones, and spills (NOTEBOOK R7.1 a).
+constexpr int SA_RD = 2;  // one-stream bench, sdf_fwdSA<true>: 0.688 ms at 2, 0.692 at 4
+template <int NW, int STEP, bool RELOAD>
+NCW_DEV void sa_mma(f32x16& acc0, f32x16& acc1, bf16x8 (&w0)[16], bf16x8 (&w1)[16], const sb_lfrag* in0, const sb_lfrag* in1,
+                    const void* n0 = nullptr, const void* n1 = nullptr, int nstride = 0, int ob = 0, int lane = 0) {
+    constexpr int RD = SA_RD, R = RD + 1;
+    bf16x8 b[R][2];
+    // the next slices' fragments through two running uniform pointers, pinned in scalar registers per unit: left as
+    // (u * nstride + ob) the 32 addresses are formed ahead of the loop as 64-bit vector pairs (64 registers: nstride is a
+    // run-time value) and the loop spills
+    const char* p0 = (const char*)n0 + (size_t)ob * 1024;
+    const char* p1 = (const char*)n1 + (size_t)ob * 1024;
+    const size_t pstep = (size_t)nstride * 1024;
+    auto reload = [&](int u) {
+        asm volatile("" : "+s"(p0), "+s"(p1));
+        w0[u] = ss_gload(p0, 0, lane);
+        if (NW == 2) w1[u] = ss_gload(p1, 0, lane);
+        p0 += pstep;
+        p1 += pstep;
+    };
+#pragma unroll
+    for (int q = 0; q < RD; ++q) { b[q][0] = in0[q * STEP]; b[q][1] = in1[q * STEP]; }
+#pragma unroll
+    for (int u = 0; u < 16; ++u) {
+        if (RELOAD && u >= 1) reload(u - 1);
+        if (u + RD < 16) { b[(u + RD) % R][0] = in0[(u + RD) * STEP]; b[(u + RD) % R][1] = in1[(u + RD) * STEP]; }
+        acc0 = NCW_MFMA_H(w0[u], b[u % R][0], acc0, 0, 0, 0);
+        acc1 = NCW_MFMA_H(w0[u], b[u % R][1], acc1, 0, 0, 0);
+        if (NW == 2) {
+            acc0 = NCW_MFMA_H(w1[u], b[u % R][0], acc0, 0, 0, 0);
+            acc1 = NCW_MFMA_H(w1[u], b[u % R][1], acc1, 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    if (RELOAD) reload(15);
+}
+
 // TRAIN = false: the forward-only render (validation / novel views / vertex colours, rendering/renderer.py:785-916 under
 // no_grad): the same arithmetic bit for bit, but of the stash only h_l (re-read by the adjoint sweep below) and feat (the
 // colour network's input) are written -- not gamma, not t_l.
@@ -505,17 +627,7 @@ __global__ __launch_bounds__(64 * SS_WAVES) void sdf_fwdS_kernel(NcwSdfNet net, 
 #pragma unroll
         for (int r = 0; r < 16; ++r) a0[r] = 0.f;
         a0 = NCW_MFMA_H(wt1, e0f, a0, 0, 0, 0);
-        ncw_lds_barrier();  // every wave is done with the split buffer (feature rows, sdf row): the plain buffers alias it
-        sb_lfrag* out = (sb_lfrag*)sbuf;  // abuf0
-#pragma unroll
-        for (int t = 0; t < SS_TILES; ++t) {
-            f32x16 sv;
-            ss_load_sprime(sv, (const SE*)st.h[L - 1], (size_t)(tile0 + t), 8, wave, lane);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sv[r] *= a0[r];
-            if (TRAIN) stash_store_block((SE*)st.t[L - 2], (size_t)(tile0 + t), 8, wave, sv, lane);
-            sb_store_units(out, t, wave, sv, lane);
-        }
+        ss_sweep_start<TRAIN>(sbuf, a0, (SE*)st.t[L - 2], (size_t)tile0, wave, lane);
 #pragma unroll
         for (int q = 0; q < 16; ++q) wa[q] = wb[q];
     }
@@ -639,19 +751,19 @@ __global__ __launch_bounds__(64 * SS_WAVES) void sdf_fwdSA_kernel(NcwSdfNet net,
         const bf16x8 wt1l = ss_gload(net.wt_lo[L - 1], (size_t)wave, lane);  // ... and its residual
         if (L - 2 >= 1) sb_load_slice<16>(wa, net.wt[L - 2], stride_of(L - 2), wave, 0, lane);
         const f32x16 bias = ss_bias(net.b_feat, wave, lane);
-        const ss_lfrag* const ain = sbuf + lane;
+        const sb_lfrag* const ain = (const sb_lfrag*)sbuf + lane;  // the hi plane: units 2 fragments apart
 #pragma unroll
         for (int tp = 0; tp < SS_TILES; tp += 2) {
             f32x16 acc0 = bias, acc1 = bias;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                acc0 = NCW_MFMA_H(wl[q], ain[((tp * 16 + q) * 2) * 64], acc0, 0, 0, 0);
-                acc1 = NCW_MFMA_H(wl[q], ain[(((tp + 1) * 16 + q) * 2) * 64], acc1, 0, 0, 0);
-            }
+            const sb_lfrag* in0 = ain + (tp * 16 * 2) * 64;
+            const sb_lfrag* in1 = ain + ((tp + 1) * 16 * 2) * 64;
+            // the last pair: the lo slice of the first sweep layer takes w_feat's registers unit by unit (this kernel runs on
+            // nets of at least 3 layers only, ncw_sdf_fwdS_launch_f16: wt_lo[L - 2] is an 8-block matrix)
+            if (tp == SS_TILES - 2) sa_mma<1, 2 * 64, true>(acc0, acc1, wl, wl, in0, in1, net.wt_lo[L - 2], nullptr, stride_of(L - 2), wave, lane);
+            else sa_mma<1, 2 * 64, false>(acc0, acc1, wl, wl, in0, in1);
             stash_store_block((SE*)st.feat, (size_t)(tile0 + tp), 8, wave, acc0, lane);
             stash_store_block((SE*)st.feat, (size_t)(tile0 + tp + 1), 8, wave, acc1, lane);
         }
-        if (L - 2 >= 1) sb_load_slice<16>(wl, net.wt_lo[L - 2], stride_of(L - 2), wave, 0, lane);
         // ---- adjoint start: a_{L-2} = W_{L-1}^T e_0 (hi + lo; the same for every point); t_{L-2} = a * phi'(z_{L-2}) ----
         bf16x8 e0f;
 #pragma unroll
@@ -662,17 +774,7 @@ __global__ __launch_bounds__(64 * SS_WAVES) void sdf_fwdSA_kernel(NcwSdfNet net,
         for (int r = 0; r < 16; ++r) a0[r] = 0.f;
         a0 = NCW_MFMA_H(wt1, e0f, a0, 0, 0, 0);
         a0 = NCW_MFMA_H(wt1l, e0f, a0, 0, 0, 0);
-        ncw_lds_barrier();  // every wave is done with the split buffer (feature rows, sdf row): the plain buffers alias it
-        sb_lfrag* out = (sb_lfrag*)sbuf;  // abuf0
-#pragma unroll
-        for (int t = 0; t < SS_TILES; ++t) {
-            f32x16 sv;
-            ss_load_sprime(sv, (const SE*)st.h[L - 1], (size_t)(tile0 + t), 8, wave, lane);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sv[r] *= a0[r];
-            if (TRAIN) stash_store_block((SE*)st.t[L - 2], (size_t)(tile0 + t), 8, wave, sv, lane);
-            sb_store_units(out, t, wave, sv, lane);
-        }
+        ss_sweep_start<TRAIN>(sbuf, a0, (SE*)st.t[L - 2], (size_t)tile0, wave, lane);
     }
     sb_lfrag* const abuf0 = (sb_lfrag*)sbuf;
     sb_lfrag* const abuf1 = abuf0 + SB_ACT / 16;
@@ -687,6 +789,9 @@ __global__ __launch_bounds__(64 * SS_WAVES) void sdf_fwdSA_kernel(NcwSdfNet net,
             bf16x8 th[8], tl[8];
             sb_load_slice<8>(th, w, stride, ob, 8 * c, lane);
             sb_load_slice<8>(tl, wlo, stride, ob, 8 * c, lane);
+            // the 16 requests stay ahead of the chunk's MFMAs: beside the 128 slice registers hipcc sank each load to its MFMA
+            // and drained the queue -- the next layer's reload with it -- 32 times per job (NOTEBOOK R8.1)
+            __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int q = 0; q < 8; ++q) {
                 const bf16x8 b = in[(jt * 16 + 8 * c + q) * 64 + lane];
@@ -698,10 +803,12 @@ __global__ __launch_bounds__(64 * SS_WAVES) void sdf_fwdSA_kernel(NcwSdfNet net,
     // ---- adjoint layers l = L-2 .. 1: t_{l-1} = ((W_hi^T + W_lo^T) t_l) * phi'(z_{l-1}) ------------------------------------
     for (int l = L - 2; l >= 1; --l) {
         const bool skip = (l == net.skip_layer);
-        const bool more = l - 1 >= 1;           // a further 8-block layer follows: its slices replace this layer's in place
-        const void* nh = more ? net.wt[l - 1] : nullptr;
-        const void* nl = more ? net.wt_lo[l - 1] : nullptr;
-        const int nstride = more ? stride_of(l - 1) : 8;
+        // a further 8-block layer follows: its slices replace this layer's in place during the last tile pair.  (ONE form: the
+        // last layer reloads its own slices, unused -- a run-time "is there a next slice" doubles the unrolled loop, NOTEBOOK R7.1 b)
+        const int ln = l - 1 >= 1 ? l - 1 : l;
+        const void* nh = net.wt[ln];
+        const void* nl = net.wt_lo[ln];
+        const int nstride = stride_of(ln);
         ncw_lds_barrier();  // t_l complete in abuf[cur]
         const sb_lfrag* in = cur ? abuf1 : abuf0;
         sb_lfrag* out = cur ? abuf0 : abuf1;
@@ -710,25 +817,20 @@ __global__ __launch_bounds__(64 * SS_WAVES) void sdf_fwdSA_kernel(NcwSdfNet net,
             f32x16 acc0, acc1;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { acc0[r] = 0.f; acc1[r] = 0.f; }
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const bf16x8 b0 = in[(tp * 16 + q) * 64 + lane], b1 = in[((tp + 1) * 16 + q) * 64 + lane];
-                acc0 = NCW_MFMA_H(wa[q], b0, acc0, 0, 0, 0);
-                acc1 = NCW_MFMA_H(wa[q], b1, acc1, 0, 0, 0);
-                acc0 = NCW_MFMA_H(wl[q], b0, acc0, 0, 0, 0);
-                acc1 = NCW_MFMA_H(wl[q], b1, acc1, 0, 0, 0);
-                if (tp == SS_TILES - 2 && more) {  // the last use of unit q in this layer: the next layer's unit q takes its registers
-                    wa[q] = ss_gload(nh, (size_t)q * nstride + wave, lane);
-                    wl[q] = ss_gload(nl, (size_t)q * nstride + wave, lane);
-                }
-            }
+            const sb_lfrag* in0 = in + (tp * 16) * 64 + lane;
+            const sb_lfrag* in1 = in + ((tp + 1) * 16) * 64 + lane;
+            // the pair's phi' operand, requested ahead of its MFMAs (and of the reload): raw 16-bit, 8 registers per tile
+            bf16x4 hr[2][4];
+            ss_request_h(hr[0], (const SE*)st.h[l], (size_t)(tile0 + tp), 8, wave, lane);
+            ss_request_h(hr[1], (const SE*)st.h[l], (size_t)(tile0 + tp + 1), 8, wave, lane);
+            if (tp == SS_TILES - 2) sa_mma<2, 64, true>(acc0, acc1, wa, wl, in0, in1, nh, nl, nstride, wave, lane);
+            else sa_mma<2, 64, false>(acc0, acc1, wa, wl, in0, in1);
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const f32x16& acc = j ? acc1 : acc0;
                 f32x16 sv;
-                ss_load_sprime(sv, (const SE*)st.h[l], (size_t)(tile0 + tp + j), 8, wave, lane);
 #pragma unroll
-                for (int r = 0; r < 16; ++r) sv[r] *= acc[r];
+                for (int r = 0; r < 16; ++r) sv[r] = ss_sprime(hr[j][r >> 2][r & 3]) * acc[r];
                 if (TRAIN) stash_store_block((SE*)st.t[l - 1], (size_t)(tile0 + tp + j), 8, wave, sv, lane);
                 sb_store_units(out, tp + j, wave, sv, lane);
             }
@@ -752,7 +854,7 @@ __global__ __launch_bounds__(64 * SS_WAVES) void sdf_fwdSA_kernel(NcwSdfNet net,
         const int f0 = 32 * jb + ncw_feat_of(r, 0);
         if (f0 >= 39) continue;  // (block 1 holds features 32..38 only)
         int comp;
-        const float dv = freq_feature_deriv<3, 6, false>(xs, f0 + 4 * h, comp);  // sinf / cosf like the value chain's gamma
+        const float dv = ss_gamma_deriv(xs[0], xs[1], xs[2], f0 + 4 * h, comp);
         const float c = gg[r] * dv;
         nx += comp == 0 ? c : 0.f;
         ny += comp == 1 ? c : 0.f;
@@ -994,6 +1096,8 @@ __global__ __launch_bounds__(64 * NS_WAVES) void nerf_refineS_kernel(NcwNerfNet 
 //              Softplus layers: the bias staging of the pipelined kernel fills the LDS);
 //   sdf_fwd:   burst 0.770-0.776 ms, pipelined 0.800-0.839 ms (its stash stores sit in the MFMA stream and share vmcnt with
 //              the weight prefetch) -> burst.
+//              (Round 8: the burst form's MFMA loops read their fragments through register rings and its sweep waits with
+//              counted vmcnt: 0.79 -> 0.69 ms per launch of the bench step, NOTEBOOK R8.1.)
 int ncw_sdf_inferS_launch_f16(const NcwSdfNet* net, const NcwPoints& src, int64_t n, float* sdf, hipStream_t st) {
     const int64_t tiles = (n + 31) / 32;
     const dim3 grid((unsigned)((tiles + SS_TILES - 1) / SS_TILES));
