@@ -1020,6 +1020,51 @@ int ncw_reproj_errors(const float* proj_dev, int n_cams, const float* xyz_dev, i
                       const int32_t* pt_idx_dev, const float* xy_dev, int64_t n_obs, const int64_t* seg_start_dev, int64_t n_seg,
                       float* err_dev, double* seg_sum_dev, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Appearance-code fit on frozen geometry (csrc/ncw_appfit.hip; appfit.py).  The reference's dataset hands out every test image
+ * as a left half to fit on and a right half to score (datasets/phototourism.py:520-556, 726-748: rays_train / rgbs_train_gt,
+ * rays_eval / rgbs_eval_gt) and has no consumer for it; this is that consumer's hot path.  With the weights frozen and
+ * perturb = 0 everything but the two colour outputs is a constant of the ray, and the rendered colour is linear in them.
+ *   ncw_appfit_loss : one wave per ray, four rays per workgroup.  weights [R, M], inside [R, S], weights_sum [R] are the cached
+ *                     outputs of ncw_composite_fwd (M = S + O with bg_rgb, else S); rgb [R*S, 3]; bg_rgb [R*M, 3] or NULL;
+ *                     background_rgb: DEVICE float[3] or NULL; target [R, 3].
+ *                         color[r]   = sum_j w_j (inside_j ? rgb_j : bg_rgb_j or 0) + background_rgb (1 - weights_sum[r])
+ *                                      -- the NcwCompositeOut.color expression of the compositor (renderer.py:751-754) in its
+ *                                      lane-strided order and wave reduction: the same bits
+ *                         ray_loss[r]= sum_c |color_c - target_c|                       (the caller sums the rays in a fixed order)
+ *                         d_rgb      = scale w_j sign(color - target) inv_denom where inside_j, 0 elsewhere        [R*S, 3]
+ *                         d_bg_rgb   = the same on the complementary samples (NULL iff bg_rgb is NULL)             [R*M, 3]
+ *                     sign(0) = 0 as torch's.  inv_denom = 1 / (R_total + 1e-5): the L1 colour loss of losses.py:25-27 with
+ *                     R_total the rays of the WHOLE fit set, not of this launch.  loss_scale: DEVICE float[2] = {scale, 1 / scale}
+ *                     (the fp16 mode's pair, NcwCompositeGrad.grad_scale_dev) or NULL = 1.  No atomics.
+ *                     Returns NCW_E_BADARG for a NULL pointer, S < 1, O < 0 or bg_rgb / d_bg_rgb not both given; 0 for R == 0.
+ *   ncw_appfit_step : sums d_a_rows [n, n_a] (the per-point code adjoints ncw_color_bwd / ncw_nerf_bwd store when given
+ *                     d_a_rows) over its n rows into grad_acc [n_a] (accumulate != 0: added to what it holds).  Fixed order:
+ *                     workgroup k sums rows [NCW_APPFIT_BLOCK_ROWS k, NCW_APPFIT_BLOCK_ROWS (k + 1)) -- a wave adds its 64 rows
+ *                     in sequence, the four waves combine as (w0 + w1) + (w2 + w3) -- into scratch, then ONE workgroup adds the
+ *                     block sums to grad_acc in block order.  Bitwise run-to-run reproducible, and bitwise independent of how
+ *                     a row sequence is split into accumulating calls as long as every call but the last holds a multiple of
+ *                     NCW_APPFIT_BLOCK_ROWS rows (any split of rows whose sums are exact in fp32, e.g. small integers).
+ *                     Two back-to-back launches (block sums; one workgroup), nothing is handed between workgroups inside a
+ *                     launch; no atomics.  n == 0 is allowed (the final call of an iteration).
+ *                     final_call != 0 then, in the same single-workgroup launch: g = grad_acc * loss_scale[1];
+ *                       any g non-finite: code and moments untouched, state->skipped += 1, loss_scale halves (>= scale_min);
+ *                       otherwise state->step += 1 and one Adam step on code [n_a] (torch.optim.Adam's arithmetic as in
+ *                       ncw_adam_step_dev: bias corrections in double, no clipping, no weight decay);
+ *                     and on an applied step the new code is broadcast into a_rows [R_rows, n_a] (what ncw_color_fwd /
+ *                     ncw_nerf_fwd read per ray).  scratch: ncw_appfit_step_scratch_floats(n, n_a) floats.
+ *                     Returns NCW_E_BADARG for n_a outside [1, NCW_APPFIT_MAX_NA], n < 0 or a missing pointer.
+ * ---------------------------------------------------------------------------------------- */
+#define NCW_APPFIT_BLOCK_ROWS 256
+#define NCW_APPFIT_MAX_NA 128
+int ncw_appfit_loss(const float* weights, const float* inside, const float* weights_sum, const float* rgb, const float* bg_rgb,
+                    const float* background_rgb, const float* target, int R, int S, int O, float inv_denom,
+                    const float* loss_scale, float* color, float* ray_loss, float* d_rgb, float* d_bg_rgb, void* stream);
+int64_t ncw_appfit_step_scratch_floats(int64_t n, int n_a);
+int ncw_appfit_step(const float* d_a_rows, int64_t n, int n_a, float* scratch, float* grad_acc, int accumulate, int final_call,
+                    float* code, float* exp_avg, float* exp_avg_sq, NcwAdamState* state, float lr, float beta1, float beta2,
+                    float eps, float* loss_scale, float scale_min, float* a_rows, int64_t R_rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

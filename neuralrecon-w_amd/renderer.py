@@ -568,11 +568,12 @@ class NeuconWRenderer:
         return self._render_with_normals(rays, ts, label, perturb_overwrite, background_rgb, cos_anneal_ratio, _rand, _z_override)[0]
 
     def _render_with_normals(self, rays, ts, label, perturb_overwrite=-1, background_rgb=None, cos_anneal_ratio=0.0, _rand=None,
-                             _z_override=None, sfm_depth_loss=True, far_override=None):
+                             _z_override=None, sfm_depth_loss=True, far_override=None, a_code=None):
         """render()'s dictionary and the compositor's per-ray normal sum_s gradients weights[:, :n_samples] [R, 3]
         (NcwCompositeOut.normals: what neuconw_system.py:445-458 sums on the host for the validation panel; views.render_view).
         sfm_depth_loss=False leaves that entry zero (its reference form selects rays on the host: a device->host sync per call);
-        far_override: see sparse_sampler.  The defaults are render()."""
+        far_override: see sparse_sampler.  a_code [n_a]: ONE appearance code for every ray instead of the embedding rows of `ts`
+        (a code fitted to a held-out image, appfit.py; detached).  The defaults are render()."""
         device = rays.device
         if not rays.is_cuda:
             raise L.NeuconwHipError("NeuconWRenderer.render: rays are not on a GPU; the hot path has no CPU fallback")
@@ -597,7 +598,11 @@ class NeuconWRenderer:
                                              L.ptr(depth_weight), L.stream_ptr(device)), "ncw_ray_prologue")
         emb_a = self.embeddings["a"]
         ordered = self.reproducible if self.reproducible is not None else (self.prec == L.PREC_F32)
-        if (not ordered and isinstance(emb_a, torch.nn.Embedding) and emb_a.padding_idx is None and emb_a.max_norm is None
+        if a_code is not None:
+            if not a_code.is_cuda:
+                raise L.NeuconwHipError("NeuconWRenderer.render: a_code is not on a GPU; the hot path has no CPU fallback")
+            a_embedded = a_code.detach().reshape(1, -1).float().expand(R, -1).contiguous()
+        elif (not ordered and isinstance(emb_a, torch.nn.Embedding) and emb_a.padding_idx is None and emb_a.max_norm is None
                 and not emb_a.sparse and emb_a.weight.dtype == torch.float32 and torch.is_grad_enabled()
                 and emb_a.weight.requires_grad and ts.dtype == torch.int64 and ts.dim() == 1):
             g = emb_a.weight.grad

@@ -169,14 +169,15 @@ def depth_colormap(depth, lut=JET, with_index=False):
 
 
 def render_view(rdr, camera, ts, chunk=DEFAULT_CHUNK, gt=None, label=None, background_rgb=None, ssim_window=3, device=None,
-                nerf_far_override=None):
+                nerf_far_override=None, a_code=None):
     """Renders one whole view with the forward-only render, chunk by chunk, without leaving the device
     (neuconw_system.py:404-464): per chunk `ncw_view_rays` -> renderer (perturb_overwrite = 0, no_grad) -> `ncw_view_store`.
     ts: ONE appearance index for the view (the image id for `val`, 1123 in tools/extract_mesh.py:157); label: semantic labels
     [H * W] (default zeros).  Returns device tensors color [3,H,W], depth [H,W], normal [3,H,W] (n / |n| / 2 + 0.5),
     depth_vis [3,H,W]; with gt ([3,H,W] or [H*W,3]) also psnr, mse, ssim as device scalars.  nerf_far_override: near / far from
     the SfM octree for this view (neuconw_system.py:407 sets it from NEUCONW.NEAR_FAR_OVERRIDE); None = the renderer's attribute.
-    The renderer's attributes are not touched."""
+    a_code [n_a]: render with this appearance code instead of the embedding row `ts` (a held-out image's fitted code, appfit.py);
+    None = the embedding row.  The renderer's attributes are not touched."""
     H, W = camera.height, camera.width
     hw = H * W
     chunk = max(1, min(int(chunk), hw))
@@ -206,8 +207,9 @@ def render_view(rdr, camera, ts, chunk=DEFAULT_CHUNK, gt=None, label=None, backg
             lab = label_all[:n] if label is None else label_all[p0:p0 + n]
             # sfm_depth_loss=False: render() reads that entry's selection back to the host (renderer.py:892-897: a
             # data-dependent shape); a view does not use it
+            kw = {} if a_code is None else {"a_code": a_code}
             out, nrm = rdr._render_with_normals(r, ts_all[:n], lab, perturb_overwrite=0, background_rgb=background_rgb,
-                                                sfm_depth_loss=False, far_override=nerf_far_override)
+                                                sfm_depth_loss=False, far_override=nerf_far_override, **kw)
             L.check(lib.ncw_view_store(L.ptr(out["color"].contiguous()), L.ptr(out["depth"].contiguous()),
                                        L.ptr(nrm.contiguous()), p0, n, hw, L.ptr(color), L.ptr(depth), L.ptr(normal),
                                        L.stream_ptr(device)), "ncw_view_store")
