@@ -1065,6 +1065,53 @@ int ncw_appfit_step(const float* d_a_rows, int64_t n, int n_a, float* scratch, f
                     float* code, float* exp_avg, float* exp_avg_sq, NcwAdamState* state, float lr, float beta1, float beta2,
                     float eps, float* loss_scale, float scale_min, float* a_rows, int64_t R_rows, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh operations (csrc/ncw_meshops.hip; meshops.py): connected components of a triangle mesh and the compaction of a face
+ * subset.  THE REFERENCE HAS NO SUCH MODE, for any entry point of this section: its reprojection filter writes a point cloud
+ * (utils/reproj_filter.py:293-300) and nothing in it labels components; the rules below are this project's.
+ * faces [F,3] int32, vertex indices below 2^31; F, V <= 2^31 - 1.
+ * CONNECTIVITY IS BY SHARED VERTEX INDEX.  Two faces that only share coordinates are NOT connected; two pieces that touch in
+ * one welded vertex ARE one component (trimesh's `split` goes by shared edges, open3d's cluster_connected_triangles by
+ * adjacent triangles: no parity with either is claimed).
+ * A face PARTICIPATES iff keep[f] != 0 (keep NULL: every face), its three corners lie in [0, V) and are pairwise distinct; the
+ * corners of any other face are never used as indices.
+ * Integer atomics only (min, add), never float atomics: all results are functions of the mesh, bitwise reproducible and
+ * independent of launch order or split.
+ *   ncw_mesh_cc_hook     : parent [V] int32 = arange(V) on entry (caller).  One lane per face unions its corners (0, 1) and
+ *                          (0, 2) in a lock-free union-find: find the two roots; hook the larger root under the smaller with
+ *                          old = atomicMin(&parent[hi], lo); if old != hi, go on with (old, lo).  Invariant parent[x] <= x at
+ *                          all times: no cycles, every retry strictly decreases an index.  No lane ever waits on another
+ *                          lane's progress: no spin loops, no locks.  Walks halve their path with the same atomicMin.  On return
+ *                          (stream order) parent holds one tree per component, root = its smallest vertex index.
+ *   ncw_mesh_cc_flatten  : parent[v] = root(v) for every v: labels.  The label of a component is the SMALLEST VERTEX INDEX IN
+ *                          IT; a vertex used by no participating face is its own label.
+ *   ncw_mesh_cc_sizes    : sizes [V] int32, ZEROED by the caller: sizes[l] = number of participating faces of the component
+ *                          with label l (taken at corner 0), 0 at every index that is not such a label.  Integer atomicAdd,
+ *                          aggregated per wave (one add per distinct label) and per workgroup (LDS) before global memory.
+ *   ncw_mesh_face_select : keep_out [F] uint8 = 1 iff the corners are in range and distinct, AND (vflags != NULL) at least
+ *                          min_corners (1..3) corners have vflags [V] uint8 != 0, AND (labels != NULL) comp_ok[labels[corner 0]]
+ *                          != 0 (labels [V] int32, comp_ok [V] uint8: both or neither); else 0.  No atomics.
+ *   ncw_mesh_compact_mark: used [V] uint8 (ZEROED by the caller): used[v] = 1 for the in-range corners of the faces with
+ *                          keep[f] != 0.  Plain stores; all writers store the same value.
+ *   (caller)             : vmap = exclusive prefix sum of used, face_offset = exclusive prefix sum of keep (0 / 1 values), both
+ *                          int32 (torch.cumsum); n_out = the number of kept faces.
+ *   ncw_mesh_compact_faces: faces_out [n_out,3] int32: row face_offset[f] = vmap of the corners of every face with keep[f] != 0
+ *                          (a corner outside [0, V) is written as -1 and vmap is not read; a face whose offset lies outside
+ *                          [0, n_out) is not written).  Kept vertices and kept faces KEEP THEIR RELATIVE ORDER.
+ * All return NCW_E_BADARG without a launch for a missing pointer, F or V outside [0, 2^31 - 1], min_corners outside 1..3, labels
+ * and comp_ok not both given, or n_out outside [0, F]; 0 without a launch for an empty range.
+ * ---------------------------------------------------------------------------------------- */
+int ncw_mesh_cc_hook(const int32_t* faces, const uint8_t* keep, int64_t n_faces, int64_t n_verts, int32_t* parent, void* stream);
+int ncw_mesh_cc_flatten(int32_t* parent, int64_t n_verts, void* stream);
+int ncw_mesh_cc_sizes(const int32_t* faces, const uint8_t* keep, int64_t n_faces, int64_t n_verts, const int32_t* labels,
+                      int32_t* sizes, void* stream);
+int ncw_mesh_face_select(const int32_t* faces, int64_t n_faces, int64_t n_verts, const uint8_t* vflags, int min_corners,
+                         const int32_t* labels, const uint8_t* comp_ok, uint8_t* keep_out, void* stream);
+int ncw_mesh_compact_mark(const int32_t* faces, const uint8_t* keep, int64_t n_faces, int64_t n_verts, uint8_t* used,
+                          void* stream);
+int ncw_mesh_compact_faces(const int32_t* faces, const uint8_t* keep, const int32_t* face_offset, const int32_t* vmap,
+                           int64_t n_faces, int64_t n_verts, int64_t n_out, int32_t* faces_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

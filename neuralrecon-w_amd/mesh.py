@@ -135,12 +135,16 @@ def sparse_volume(sparse_data, sdf_values):
 
 @torch.no_grad()
 def extract_mesh(renderer, dim, scene_radius, scene_origin, origin=None, radius=1.0, with_color=False, embedding_a=None,
-                 level=0.0, chunk_rgb=1 << 16, sparse_data=None, chunk=1 << 22, group=None):
+                 level=0.0, chunk_rgb=1 << 16, sparse_data=None, chunk=1 << 22, group=None, min_component_faces=0,
+                 largest_components=None):
     """utils/visualization.py:37-159.  Dense path: the [dim]^3 lattice over `origin` +- `radius` (training coordinates), swept
     on chip and sharded over the ranks (grid.sdf_grid).  Sparse path (`sparse_data` from gen_grid_spc): the SDF only at the
     sub-voxels of the occupied octree voxels (sharded like neuconw_system.py:236-256), marching cubes under the all-8-corners
     mask.  Returns dict(vertices [V,3] world coordinates, faces [F,3], vertices_training, colors [V,3] uint8 or None) as GPU
-    tensors, on every rank (the reference returns the mesh on rank 0 only)."""
+    tensors, on every rank (the reference returns the mesh on rank 0 only).
+    min_component_faces > 0 / largest_components = K (not in the reference; both off: this path is not taken): after marching
+    cubes and BEFORE the colour pass, only the connected components (by shared vertex index, meshops.clean) of at least that
+    many faces / the K with the most faces are kept, so the colour network never runs on floaters."""
     dev = next(renderer.neuconw.parameters()).device
     so = torch.as_tensor(np.asarray(scene_origin, dtype=np.float32), device=dev).reshape(3)
     if sparse_data is None:
@@ -162,6 +166,11 @@ def extract_mesh(renderer, dim, scene_radius, scene_origin, origin=None, radius=
         vo_sfm = torch.from_numpy(np.asarray(sparse_data["vol_origin"], dtype=np.float64)).float().to(dev)  # :53
         vol_origin = (vo_sfm - so) / float(scene_radius)                         # :59
         voxel_size = float(sparse_data["voxel_size"]) / float(scene_radius)      # :61
+    if (int(min_component_faces) > 0 or largest_components is not None) and faces.shape[0] > 0:
+        from . import meshops
+
+        verts, faces, _, _ = meshops.clean(verts, faces, None, min_component_faces, largest_components)
+        faces = faces.long()
     verts_t = verts * voxel_size + vol_origin                                    # :116
     verts_w = verts_t * float(scene_radius) + so                                 # :117
     colors = None

@@ -21,7 +21,7 @@ import numpy as np
 import torch
 import yaml
 
-from . import colmap, evalmesh, ply
+from . import colmap, evalmesh, meshops, ply
 from . import lib as L
 # The names the test suites of the earlier commits call (tests/test_reproj_host.py, tests/test_gpu_reproj*.py, tests/test_gpu_surf.py):
 # bindings only -- the functions live in colmap.py / ply.py, and the package's own code calls them there.
@@ -372,7 +372,7 @@ def render_cloud_depth(points, scene_config, voxel_size, K, pose, height, width,
 
 @torch.no_grad()
 def reproj_filter(src_file, target_file, data_path, output_path, gt=False, voxel_size=0.01, visualize=False, znear=ZNEAR,
-                  zfar=ZFAR, cull="back", device=None, verbose=True):
+                  zfar=ZFAR, cull="back", device=None, verbose=True, keep_faces=False, min_corners=1, min_component_faces=0):
     """utils/reproj_filter.py: keep the vertices of target_file that a training view of data_path sees on src_file.
     A source WITH faces (a mesh).  Per view: render the depth of the source mesh, back-project every pixel with depth > 0
     at its integer pixel coordinates, mark the nearest target vertex when it is closer than 2 sqrt(2) voxel_size (GT units).
@@ -386,7 +386,20 @@ def reproj_filter(src_file, target_file, data_path, output_path, gt=False, voxel
     undefined otherwise).  The nearest-neighbour marking and its 2 sqrt(2) voxel_size are not used on this path (:224-225);
     znear / zfar / cull do not apply.  A pixel that misses marks nothing and has depth 0 (the reference's wrap-around of
     pid = -1 and its depth of 0.02 there are not reproduced).
-    Returns (xyz float64 [K,3], rgb uint8 [K,3])."""
+    `keep_faces` (default off; the reference has no such mode, the rule is this project's): the TARGET file must have faces
+    (ValueError before any view is rendered otherwise), and <output_path>/reprojected_mesh.ply is written IN ADDITION to
+    reprojected.ply, which stays byte for byte what it is without the option.  After all views are marked, from the same
+    per-vertex flags reprojected.ply is written from (mesh source: Target.flags; point-cloud source: VoxelCloud.select):
+    meshops.face_select keeps a target face iff at least `min_corners` (1..3) of its corners are marked, then -- with
+    min_component_faces > 0 -- only the faces of connected components (by shared vertex index, over the kept faces) of at
+    least that many faces, then meshops.submesh compacts: the vertices some kept face uses, in FILE ORDER (no np.unique, no
+    welding), GT coordinates as doubles, uchar colours (zeros without), faces remapped.
+    Why min_corners = 1 is the default: every back-projected pixel marks ONE nearest vertex, so where the mesh is finer than
+    the pixels a visible triangle rarely has all three corners marked; a strict rule would punch holes that a surface-based
+    recall then counts against the model.  The one-ring rule admits at most one triangle's width of surface beyond the marked
+    vertices.  min_corners = 3 is for whoever wants "nothing the reference would drop": its vertex set is a subset of the
+    rows of reprojected.ply.
+    Returns (xyz float64 [K,3], rgb uint8 [K,3]) -- the rows of reprojected.ply, whatever keep_faces is."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     log = print if verbose else (lambda *a, **k: None)
     os.makedirs(output_path, exist_ok=True)
@@ -397,7 +410,12 @@ def reproj_filter(src_file, target_file, data_path, output_path, gt=False, voxel
     views = load_views(data_path, S)
     log("views to process: %d" % len(views))
 
-    t_xyz, _, t_rgb = ply.read_mesh(target_file)
+    t_xyz, t_faces, t_rgb = ply.read_mesh(target_file)
+    if keep_faces:
+        if int(min_corners) not in (1, 2, 3):
+            raise ValueError("reproj_filter: min_corners must be 1, 2 or 3 (got %r)" % (min_corners,))
+        if t_faces.shape[0] == 0:
+            raise ValueError("reproj_filter: keep_faces needs a target with faces; %s has none" % target_file)
     if not gt:
         t_xyz = evalmesh.apply_transform(t_xyz, S)
     if t_rgb is None:
@@ -406,10 +424,12 @@ def reproj_filter(src_file, target_file, data_path, output_path, gt=False, voxel
     s_verts, s_faces, _ = ply.read_mesh(src_file)
     if s_faces.shape[0] == 0:
         log("reproject point cloud")
-        xyz, rgb = _filter_cloud(s_verts if gt else evalmesh.apply_transform(s_verts, S), t_xyz, t_rgb, views, scene_config,
-                                 output_path, voxel_size, visualize, dev)
+        xyz, rgb, flags = _filter_cloud(s_verts if gt else evalmesh.apply_transform(s_verts, S), t_xyz, t_rgb, views, scene_config,
+                                        output_path, voxel_size, visualize, dev, with_flags=True)
         ply.write(os.path.join(output_path, "reprojected.ply"), xyz, rgb=rgb)
         log("kept %d of %d vertices" % (xyz.shape[0], t_xyz.shape[0]))
+        if keep_faces:
+            _write_filtered_mesh(output_path, t_xyz, t_faces, t_rgb, flags, min_corners, min_component_faces, dev, log)
         return xyz, rgb
     target = Target(t_xyz, t_rgb, 2 * np.sqrt(2) * voxel_size, dev)
     mesh = RasterMesh(s_verts, s_faces, dev)
@@ -437,13 +457,35 @@ def reproj_filter(src_file, target_file, data_path, output_path, gt=False, voxel
     xyz, rgb = target.rows()
     ply.write(os.path.join(output_path, "reprojected.ply"), xyz, rgb=rgb)
     log("kept %d of %d vertices" % (xyz.shape[0], target.m))
+    if keep_faces:
+        _write_filtered_mesh(output_path, target.xyz, t_faces, target.rgb, target.flags[: target.m], min_corners,
+                             min_component_faces, dev, log)
     return xyz, rgb
 
 
-def _filter_cloud(s_xyz, t_xyz, t_rgb, views, scene_config, output_path, voxel_size, visualize, dev):
+def _write_filtered_mesh(output_path, xyz, faces, rgb, flags, min_corners, min_component_faces, dev, log):
+    """reprojected_mesh.ply of reproj_filter(keep_faces=True): the target's faces (xyz [V,3] float64 in GT coordinates, faces
+    [F,3], rgb uint8 [V,3] or None, numpy) with at least min_corners corners set in flags ([V] on the device), optionally only
+    the components of at least min_component_faces kept faces, compacted in file order."""
+    xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+    V = xyz.shape[0]
+    rgb = np.zeros((V, 3), dtype=np.uint8) if rgb is None else np.asarray(rgb, dtype=np.uint8).reshape(-1, 3)
+    f = torch.from_numpy(np.ascontiguousarray(faces, dtype=np.int64)).to(dev)
+    flags = (flags != 0).to(torch.uint8)
+    keep = meshops.face_select(f, V, vflags=flags, min_corners=min_corners)
+    if int(min_component_faces) > 0:
+        labels, sizes = meshops.components(f, V, keep)
+        ok = meshops.select_components(sizes, min_faces=int(min_component_faces))
+        keep = meshops.face_select(f, V, vflags=flags, min_corners=min_corners, labels=labels, comp_ok=ok)
+    v, fo, c, _ = meshops.submesh(torch.from_numpy(xyz).to(dev), f, keep, torch.from_numpy(rgb).to(dev))
+    ply.write(os.path.join(output_path, "reprojected_mesh.ply"), v.cpu().numpy(), fo.cpu().numpy(), rgb=c.cpu().numpy())
+    log("kept %d of %d faces (%d vertices)" % (fo.shape[0], f.shape[0], v.shape[0]))
+
+
+def _filter_cloud(s_xyz, t_xyz, t_rgb, views, scene_config, output_path, voxel_size, visualize, dev, with_flags=False):
     """The point-cloud source of reproj_filter (source and target already in GT coordinates; scene_config: the parsed
     config.yaml): one trace per view with the pose inv(E inv(sfm2gt)), one select over the target at the end; the unique
-    rows of the kept vertices."""
+    rows of the kept vertices (with_flags: and the per-vertex flags they were taken from, bool [N] on the device)."""
     cloud = VoxelCloud(s_xyz, scene_config, voxel_size, dev)
     depth = None
     for v in views:
@@ -461,7 +503,9 @@ def _filter_cloud(s_xyz, t_xyz, t_rgb, views, scene_config, output_path, voxel_s
                       pts.double().cpu().numpy() + cloud.origin)
     t_xyz = np.ascontiguousarray(t_xyz, dtype=np.float64).reshape(-1, 3)
     rgb = np.zeros(t_xyz.shape, dtype=np.uint8) if t_rgb is None else np.asarray(t_rgb, dtype=np.uint8).reshape(-1, 3)
-    return unique_rows(t_xyz, rgb, cloud.select(t_xyz), dev)
+    flags = cloud.select(t_xyz)
+    rows = unique_rows(t_xyz, rgb, flags, dev)
+    return rows + (flags,) if with_flags else rows
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -477,24 +521,37 @@ SCENES = {
 
 
 def eval_pipeline(scene_name, pred_dir, data_root="data/heritage-recon", verbose=True, surface=None, surface_seed=0,
-                  surface_mode="stratified", error_clouds=None):
+                  surface_mode="stratified", error_clouds=None, keep_faces=False, min_corners=1, min_component_faces=0,
+                  exact_recall=False):
     """scripts/eval_pipeline.sh in one process: the reprojection filter of <pred_dir>/mesh/extracted_mesh_level_10_colored.ply
     against itself (written to <pred_dir>/mesh/reprojected.ply), then evalmesh.eval_mesh of that file against
     <data_root>/<scene>/<scene>.ply with the scene's thresholds and the SfM crop of <data_root>/<scene>/neuralsfm, results in
     <pred_dir>/mesh/eval_<scene>_reprojected.ply/.  surface / surface_seed / surface_mode / error_clouds go to eval_mesh as
-    they are (reprojected.ply is a point cloud, so `surface` is refused there).  Returns the last threshold's metrics."""
+    they are (reprojected.ply is a point cloud, so `surface` is refused there).  Returns the last threshold's metrics.
+    keep_faces (default off; not in the reference): filter with reproj_filter(keep_faces=True, min_corners,
+    min_component_faces) and score <pred_dir>/mesh/reprojected_mesh.ply instead, results in eval_<scene>_reprojected_mesh.ply/;
+    `surface` and `exact_recall` then go to eval_mesh and work, because that file has faces.  Without keep_faces
+    exact_recall is refused (ValueError): reprojected.ply is a point cloud."""
     if scene_name not in SCENES:
         raise ValueError("Not supported scene: %s (one of %s)" % (scene_name, ", ".join(sorted(SCENES))))
+    if exact_recall and not keep_faces:
+        raise ValueError("--exact_recall needs a triangle mesh: without --keep_faces the pipeline scores mesh/reprojected.ply, "
+                         "a point cloud")
     sc = SCENES[scene_name]
     pred_path = os.path.join(pred_dir, "mesh")
     scene_dir = os.path.join(data_root, scene_name)
     mesh_file = os.path.join(pred_path, "extracted_mesh_level_10_colored.ply")
-    reproj_filter(mesh_file, mesh_file, scene_dir, pred_path, verbose=verbose)
+    if not os.path.isfile(mesh_file):  # before anything is created or a GPU is touched
+        raise FileNotFoundError("No such file: %s (the run directory holds no extracted mesh)" % mesh_file)
+    reproj_filter(mesh_file, mesh_file, scene_dir, pred_path, verbose=verbose, keep_faces=keep_faces, min_corners=min_corners,
+                  min_component_faces=min_component_faces)
     with open(os.path.join(scene_dir, "config.yaml")) as fh:
         scene_config = yaml.safe_load(fh)
     sfm = {"path": os.path.join(scene_dir, "neuralsfm"), "track_length": sc["track_length"],
            "reproj_error": sc["reproj_error"], "voxel_size": sc["voxel_size"]}
-    return evalmesh.eval_mesh(os.path.join(pred_path, "reprojected.ply"), os.path.join(scene_dir, scene_name + ".ply"),
+    scored = "reprojected_mesh.ply" if keep_faces else "reprojected.ply"
+    return evalmesh.eval_mesh(os.path.join(pred_path, scored), os.path.join(scene_dir, scene_name + ".ply"),
                               scene_config, False, threshold=evalmesh.parse_thresholds(sc["thresholds"]), bbx_name="eval_bbx",
-                              save_name=scene_name + "_reprojected.ply", sfm=sfm, verbose=verbose, surface=surface,
-                              surface_seed=surface_seed, surface_mode=surface_mode, error_clouds=error_clouds)
+                              save_name=scene_name + "_" + scored, sfm=sfm, verbose=verbose, surface=surface,
+                              surface_seed=surface_seed, surface_mode=surface_mode, error_clouds=error_clouds,
+                              exact_recall=exact_recall)

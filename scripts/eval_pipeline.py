@@ -14,6 +14,10 @@ already in GT coordinates: the two steps chain correctly only when sfm2gt is the
 The file the pipeline scores, reprojected.ply, is a point cloud: --sample_surface needs faces and is refused on it, and so
 is --exact_recall (exact point-to-triangle recall, scripts/eval_mesh.py), before any work: the reprojection filter does not
 keep the faces.
+
+--keep_faces (not in the reference) [--min_corners 1|2|3] [--min_component_faces N] makes the filter keep them: it also writes
+<pred_dir>/mesh/reprojected_mesh.ply (scripts/reproj_filter.py --keep_faces), the pipeline scores THAT file, with results in
+<pred_dir>/mesh/eval_<scene>_reprojected_mesh.ply/, and --sample_surface and --exact_recall work on it.
 """
 import argparse
 import os
@@ -35,20 +39,28 @@ def parse_args(argv=None):
     ap.add_argument("--error_clouds", default=False, action="store_true",
                     help="write the error-coloured clouds of every threshold")
     ap.add_argument("--exact_recall", default=False, action="store_true",
-                    help="refused here: reprojected.ply has no faces (score a mesh with scripts/eval_mesh.py --exact_recall)")
+                    help="needs --keep_faces; refused without: reprojected.ply has no faces (or score a mesh with "
+                         "scripts/eval_mesh.py --exact_recall)")
+    ap.add_argument("--keep_faces", default=False, action="store_true",
+                    help="keep the faces through the filter and score reprojected_mesh.ply")
+    ap.add_argument("--min_corners", type=int, choices=[1, 2, 3], default=1, help="--keep_faces: marked corners a face needs")
+    ap.add_argument("--min_component_faces", type=int, default=0,
+                    help="--keep_faces: drop connected components of fewer kept faces")
     return ap.parse_args(argv)
 
 
 def main(argv=None):
     args = parse_args(argv)
-    if args.exact_recall:
+    if args.exact_recall and not args.keep_faces:
         raise SystemExit("--exact_recall needs a triangle mesh: the pipeline scores mesh/reprojected.ply, a point cloud (the "
                          "reprojection filter does not keep the faces).  Score the mesh itself with scripts/eval_mesh.py "
                          "--exact_recall.")
     print("Evaluating %s ..." % args.pred_dir)
     reproj.eval_pipeline(args.scene_name, args.pred_dir, args.data_root, surface=args.sample_surface,
                          surface_seed=args.surface_seed, surface_mode=args.surface_mode,
-                         error_clouds=True if args.error_clouds else None)
+                         error_clouds=True if args.error_clouds else None, keep_faces=args.keep_faces,
+                         min_corners=args.min_corners, min_component_faces=args.min_component_faces,
+                         exact_recall=args.exact_recall)
 
 
 if __name__ == "__main__":

@@ -12,7 +12,10 @@ kaolin, skimage or trimesh -- one process per GPU.
     --eval_level > 0: the sparse grid of `gen_grid_spc` (:60-102) -- the sub-voxels of the occupied voxels of the training
     octree (COLMAP points, voxel.octree_from_sfm) at that level; the SDF only there, cubes with all 8 corners evaluated;
   * marching cubes, vertex welding, the vertex-colour pass (`renderer.rgb` viewed along +z with appearance code 1123, :148) and the
-    binary PLY on the GPU of rank 0 (mesh.py); file name and directory follow :112-114,160-167.
+    binary PLY on the GPU of rank 0 (mesh.py); file name and directory follow :112-114,160-167;
+  * --min_component_faces N / --largest_components K (not in the reference): after marching cubes and BEFORE the colour pass,
+    drop the connected components (by shared vertex, meshops.py) of fewer than N faces / keep the K with the most faces; the
+    file name is unchanged.
 """
 import argparse
 import os
@@ -41,6 +44,8 @@ def main():
     ap.add_argument("--chunk_rgb", type=int, default=1 << 16, help="vertices per launch of the colour pass")
     ap.add_argument("--ckpt_path", required=True, help="checkpoint in the reference's layout (trainer.save_checkpoint / PL)")
     ap.add_argument("--out_dir", default=None, help="default: results/<dataset_name>/<ckpt dir>_<ckpt name>/mesh")
+    ap.add_argument("--min_component_faces", type=int, default=0, help="drop connected components of fewer faces (floaters)")
+    ap.add_argument("--largest_components", type=int, default=None, help="keep the K components with the most faces")
     ap.add_argument("--prec", default=None, choices=["bf16", "f16", "f32"], help="default: fp32 for the colour pass, SDFNetwork.value_prec() for the SDF lattice")
     args = ap.parse_args()
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
@@ -75,7 +80,8 @@ def main():
     a = emb(torch.ones(1, device=dev, dtype=torch.long) * 1123) if args.vertex_color else None  # tools/extract_mesh.py:148
     m = mesh.extract_mesh(rdr, args.mesh_size, scene["radius"], scene["origin"], origin=origin, radius=args.mesh_radius,
                           with_color=args.vertex_color, embedding_a=a, chunk_rgb=args.chunk_rgb, sparse_data=sparse,
-                          chunk=args.chunk)
+                          chunk=args.chunk, min_component_faces=args.min_component_faces,
+                          largest_components=args.largest_components)
     if rank == 0:
         save_name = "_".join(os.path.normpath(args.ckpt_path).split(os.sep)[-2:]).replace(".ckpt", "")
         out_dir = args.out_dir or os.path.join("results", args.dataset_name, save_name, "mesh")

@@ -9,6 +9,9 @@ open3d, trimesh or ray -- keeps the vertices of --target_file that some training
   * a --src_file without faces is a point cloud: it is voxelised over the scene's eval_bbx at --voxel_size and every view is
     traced to the first occupied voxel; a target vertex is kept iff its voxel was some pixel's first hit (INTEGRATION.md);
   * writes <output_path>/reprojected.ply (double x / y / z, uchar colours), in GT coordinates;
+  * --keep_faces (not in the reference) also writes <output_path>/reprojected_mesh.ply: the target's faces with at least
+    --min_corners marked corners (default 1), optionally without the connected components of fewer
+    than --min_component_faces faces, vertices in file order; reprojected.ply is unchanged by it;
   * --visualize writes render/depth/<name>.npy and render/reprojects/<name>.ply (the reference writes JPEGs);
   * --n_cpus / --n_gpus are accepted for compatibility and ignored: one process renders every view on one GPU.
 """
@@ -33,6 +36,12 @@ def parse_args(argv=None):
     ap.add_argument("--znear", type=float, default=reproj.ZNEAR, help="near plane (pyrender's default)")
     ap.add_argument("--zfar", type=float, default=reproj.ZFAR, help="far plane (pyrender's default)")
     ap.add_argument("--cull", choices=sorted(reproj.CULL), default="back", help="face culling (pyrender: back)")
+    ap.add_argument("--keep_faces", default=False, action="store_true",
+                    help="also write reprojected_mesh.ply: the target's faces with marked corners (the target needs faces)")
+    ap.add_argument("--min_corners", type=int, choices=[1, 2, 3], default=1,
+                    help="--keep_faces: marked corners a face needs (1: one-ring rule, 3: nothing the reference would drop)")
+    ap.add_argument("--min_component_faces", type=int, default=0,
+                    help="--keep_faces: drop connected components (by shared vertex) of fewer kept faces")
     ap.add_argument("--n_cpus", type=int, default=1, help="ignored (accepted for compatibility): one process")
     ap.add_argument("--n_gpus", type=int, default=4, help="ignored (accepted for compatibility): one GPU")
     return ap.parse_args(argv)
@@ -42,7 +51,8 @@ def main(argv=None):
     args = parse_args(argv)
     reproj.reproj_filter(args.src_file, args.target_file or args.src_file, args.data_path, args.output_path, gt=args.gt,
                          voxel_size=args.voxel_size, visualize=args.visualize, znear=args.znear, zfar=args.zfar,
-                         cull=args.cull)
+                         cull=args.cull, keep_faces=args.keep_faces, min_corners=args.min_corners,
+                         min_component_faces=args.min_component_faces)
 
 
 if __name__ == "__main__":
