@@ -267,7 +267,8 @@ int ncw_color_fwd(const NcwColorNet* net, int prec, const NcwPoints* pts, int64_
  * d_a_rows: NULL, or [n,n_a] -- then every point's appearance-code adjoint is STORED as its row instead of being
  * added to d_a with atomics, and ncw_ray_sum_rows reduces the rows of a ray in sample order (reproducible; the
  * fp32 parity mode uses it).
- * and the z-stashes for ncw_wgrad. */
+ * and the z-stashes for ncw_wgrad.
+ * Both return, without a launch, NCW_E_UNSUPPORTED for NcwPoints mode 4 and NCW_E_BADARG for prec = f32 with w_f_lo set. */
 int ncw_color_bwd(const NcwColorNet* net, int prec, const NcwPoints* pts, int64_t n, const float* rgb,
                   const float* d_rgb, float* d_grad, float* d_a, float* d_a_rows, void* dfeat_stash,
                   const NcwColorStash* stash, void* stream);

@@ -456,6 +456,7 @@ extern "C" int NCW_FN(ncw_color_bwd)(const NcwColorNet* net, int prec, const Ncw
     if (!color_ok(net) || !pts || !stash || n < 0 || (prec != NCW_PREC_F32 && prec != NCW_PREC_BF16)) return NCW_E_BADARG;
     if (pts->mode == 4) return NCW_E_UNSUPPORTED;  // point selections: background NeRF kernels only
     if (n == 0) return 0;
+    if (net->w_f_lo != nullptr && prec == NCW_PREC_F32) return NCW_E_BADARG;  // residual matrices are 16-bit: ncw_color_fwd refuses it too
     hipStream_t st = (hipStream_t)stream;
     NCW_COLOR_DISPATCH(color_bwd_kernel, *net, *pts, n, rgb, d_rgb, d_grad, d_a, d_a_rows, dfeat_stash, *stash);
     return 0;
