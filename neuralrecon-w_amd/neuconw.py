@@ -130,6 +130,8 @@ class SDFNetwork(_PackedNet):
         dims = [d_in] + [d_hidden for _ in range(n_layers)] + [d_out]
         dims[0] = 3 + 3 * 2 * multires
         self.num_layers = len(dims)
+        if self.num_layers - 1 > L.MAX_LAYERS:
+            raise NotImplementedError("HIP SDF kernels hold at most %d Linears (n_layers <= %d)" % (L.MAX_LAYERS, L.MAX_LAYERS - 1))
         self.skip_in = tuple(skip_in) if skip_in is not None else ()
         if len(self.skip_in) > 1 or any(s <= 0 or s >= self.num_layers - 2 for s in self.skip_in):
             raise NotImplementedError("at most one skip connection into a hidden layer is supported")

@@ -215,7 +215,11 @@ class PackPlan:
         grad_mul (host float) and grad_mul_dev (1-element device tensor, read at run time) multiply everything written
         (1 / loss scale in the fp16 mode)."""
         gm_ptr = grad_mul_dev.data_ptr() if grad_mul_dev is not None else 0
-        key = (bool(accumulate), float(grad_mul), gm_ptr) + tuple(accumulate_into[id(u["weight"])].data_ptr() for u in self._unpack) \
+        # every address the table holds: the gradient tensors of weight, gain AND bias (a caller that passes fresh tensors can get
+        # the weight gradients' blocks back from the allocator while the small ones move: a hit on the weights alone wrote d_g / d_bias
+        # through stale pointers)
+        key = (bool(accumulate), float(grad_mul), gm_ptr) \
+            + tuple(accumulate_into[id(u[k])].data_ptr() if u[k] is not None else 0 for u in self._unpack for k in ("weight", "g", "bias")) \
             + tuple(u["weight"].data_ptr() for u in self._unpack)
         cache = self.__dict__.setdefault("_unpack_cache", {})
         hit = cache.get(key)
