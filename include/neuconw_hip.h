@@ -798,6 +798,49 @@ int ncw_cache_rows(const NcwViewCamera* cam, const uint8_t* image, const uint8_t
                    void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Ray source (csrc/ncw_source.hip): a training batch rebuilt from the scene itself instead of gathered from cached rows --
+ * what ncw_cache_rows (datasets/phototourism.py:557-657) followed by ncw_batch_assemble (datasets/phototourism.py:709-726 +
+ * the black-list test of neuconw_system.py:345-349) returns for the same rays, bit for bit, from 8 bytes per kept ray.
+ *   recs [n_rows]        : NcwSourceRec, one per kept ray, grouped by image in table order:
+ *                            pix   bits 0..30 = row-major pixel index in its image (row = pix / width, col = pix % width);
+ *                                  bit 31 set = the pixel carries an SfM key-point (an entry of the key-point table);
+ *                            r, g, b = the image's uint8 pixel (rgbs = float(u8) / 255.f, as ncw_cache_rows writes it);
+ *                            label = the label-map sample ncw_cache_rows put in the row; 0 when the source has no label maps.
+ *   images [n_img]       : NcwSourceImage = the view (with the camera's own near / far) and ts = the COLMAP image id.
+ *   row_start [n_img + 1]: int64, records [row_start[k], row_start[k + 1]) belong to image k; an image without a record repeats
+ *                          the previous start.  row_start[0] = 0, row_start[n_img] = n_rows.
+ *   kp_start [n_img + 1] : int64, the same for the key-point table: kp_pix (int32, ascending within an image), kp_depth (f32, the
+ *                          along-ray depth as ncw_cache_rows writes it), kp_weight (f32).  Only records with bit 31 search it (a
+ *                          binary search over the image's segment); a record whose pixel is not found gets depth = weight = 0.
+ *                          The three arrays may be NULL when no record has bit 31 set.
+ *   range, voxel_size    : the range octree (HOST struct) or NULL.  A record exists only for a pixel the hit octree kept, so only
+ *                          this one is walked: near = rn, far = rn > 0 ? rf + voxel_size : rf.  NULL: the camera's near / far.
+ *   idx [B]              : int64 record indices, clamped to [0, n_rows) as ncw_batch_assemble clamps; NULL = the identity.
+ *   outputs              : ncw_batch_assemble's -- rays [B][11] = o(3) d(3) near far depth weight 0, ts [B] int64, label [B]
+ *                          int64 or NULL, rgbs [B][3], keep [B] uint8 or NULL (0 where with_semantics and label is one of the
+ *                          n_ids <= 4 HOST mask_ids).  with_semantics == 0: label = 0 and keep = 1.
+ * One lane per batch row, one launch per batch; o, d, near, far come from the device functions ncw_cache_rows uses
+ * (csrc/ncw_rowmath.h).  No atomics: bitwise reproducible and independent of how a set of indices is split into launches.
+ * rays and rgbs must be 16-byte aligned (workgroups write 16-byte stores).  Returns NCW_E_BADARG for NULL / misaligned pointers,
+ * n_rows <= 0, n_img <= 0, n_ids outside 0..4 or a bad octree; 0 without a launch for B <= 0.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct NcwSourceRec {
+    uint32_t pix;
+    uint8_t r, g, b, label;
+} NcwSourceRec;
+
+typedef struct NcwSourceImage {
+    NcwViewCamera cam;
+    int32_t ts;
+    int32_t _pad;
+} NcwSourceImage;
+
+int ncw_source_batch(const NcwSourceRec* recs, int64_t n_rows, const NcwSourceImage* images, const int64_t* row_start,
+                     const int64_t* kp_start, int n_img, const int32_t* kp_pix, const float* kp_depth, const float* kp_weight,
+                     const NcwCacheOctree* range, float voxel_size, const int64_t* idx, int64_t B, int with_semantics, float* rays,
+                     int64_t* ts, int64_t* label, float* rgbs, const int* mask_ids, int n_ids, uint8_t* keep, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Voxel first-hit views (csrc/ncw_voxview.hip): the point-cloud source of the reprojection filter.  The reference voxelises
  * the source cloud over the evaluation box (utils/kaolin_renderer.py:16-17: gen_octree(..., expand=0, in_sfm=False)), traces
  * every pixel of every training view to the first occupied voxel (:110-141) and keeps the target points whose voxel some

@@ -291,29 +291,19 @@ def write_cache(all_rays, all_rgbs, root_dir, cache_dir="cache", img_downscale=1
     return files
 
 
-def build_cache(root_dir, cache_dir="cache", img_downscale=1, semantic_map_path=None, split_to_chunks=-1, sfm_path=None, seed=0,
-                device=None, cache_type="npz", depth_percent=None, use_voxel=True, scene_origin=None, scene_radius=None,
-                stats=None):
-    """tools/prepare_data/prepare_data_cache.py for the training images (`split != "test"`) of the scene at root_dir: writes
-    <root_dir>/<cache_dir>/splits/split_i/{rays,rgbs}N.npz + {rays,rgbs}N_meta_info.json (split_to_chunks > 0) or one
-    raysN.npz / rgbsN.npz.  Returns the files written.
-      * sfm_path: the COLMAP model under dense/ (None: the reference's per-scene choice, views.reference_sfm_path);
-      * semantic_map_path: directory (under root_dir) of the per-image label maps; None = 12-column rows without labels;
-      * depth_percent: None = the reference's per-scene value (`DEPTH_PERCENT`, else 0);
-      * use_voxel: near / far and the ray selection from the two SfM octrees of config.yaml (the reference's default);
-      * seed: every random draw (depth padding per image, chunk padding) comes from generators seeded with it;
-      * stats: an optional dict that receives timings (host decode, device, device -> host bytes, file writing)."""
+def open_scene(root_dir, img_downscale=1, sfm_path=None, device=None, depth_percent=None, use_voxel=True, who="build_cache"):
+    """What `build_cache` reads and builds ONCE per scene, before its loop over the training images -- shared with
+    raysource.RaySource.from_scene, so both start from the same readers, octrees and defaults.  Returns a dict: `root_dir`
+    (normalised), `img_downscale`, `device`, `scene` (views.read_scene), `depth_percent` (None resolved to the reference's
+    per-scene value), `xyz_table` / `err_table`, `hit` / `range` (the two SfM octrees, None without use_voxel), `voxel_size`."""
     import yaml
 
-    if cache_type != "npz":
-        raise NotImplementedError("cache_type %r: only npz is written (h5py is not a dependency, and raycache.RayCache and the "
-                                  "reference's config/defaults.py read npz); pass cache_type='npz'" % (cache_type,))
     img_downscale = int(img_downscale)
     if img_downscale < 1:
         raise ValueError("image can only be downsampled, please set img_downscale>=1!")
     device = torch.device("cuda" if device is None else device)
     if device.type != "cuda":
-        raise L.NeuconwHipError("cachebuild.build_cache: not a GPU device; the ray cache has no CPU fallback")
+        raise L.NeuconwHipError("cachebuild.%s: not a GPU device; the ray cache has no CPU fallback" % who)
     root_dir = os.path.normpath(root_dir)
     scene = views.read_scene(root_dir, sfm_path, with_points=True)
     if depth_percent is None:
@@ -329,31 +319,62 @@ def build_cache(root_dir, cache_dir="cache", img_downscale=1, semantic_map_path=
                                     radius=1)
         rng = voxel.octree_from_sfm(root_dir, cfg["min_track_length"], voxel_size, device, sfm_path=scene["sfm_path"], expand=2,
                                     radius=1.5)
-    gen = torch.Generator().manual_seed(int(seed))
-    all_rays, all_rgbs = [], []
-    st = {"n_images": 0, "n_pixels": 0, "n_rays": 0, "d2h_bytes": 0, "t_decode": 0.0, "t_device": 0.0, "t_write": 0.0}
+    return {"root_dir": root_dir, "img_downscale": img_downscale, "device": device, "scene": scene, "depth_percent": depth_percent,
+            "xyz_table": xyz_table, "err_table": err_table, "hit": hit, "range": rng, "voxel_size": voxel_size}
+
+
+def scene_items(sc, semantic_map_path=None, scene_origin=None, scene_radius=None, stats=None):
+    """The loop of `build_cache` over the training images (`split != "test"`) of an `open_scene` dict, up to the device work:
+    yields `build_image`'s arguments per image -- (camera, decoded uint8 image, image id, key-point tuple, w2c, label map or
+    None).  stats: a dict whose `t_decode` receives the host decode time."""
+    root_dir, scene, img_downscale = sc["root_dir"], sc["scene"], sc["img_downscale"]
     for image_id in scene["ids_train"]:
         name = scene["images"][image_id]["name"]
         t0 = time.perf_counter()
         img = views._decode_image(os.path.join(root_dir, "dense", "images", name), img_downscale)
         h, w = img.shape[:2]
         lab = load_label_map(root_dir, semantic_map_path, name, w, h, img_downscale) if semantic_map_path is not None else None
-        t1 = time.perf_counter()
+        if stats is not None:
+            stats["t_decode"] = stats.get("t_decode", 0.0) + time.perf_counter() - t0
         K, w2c, c2w, _, _ = views.image_pose(scene, image_id, img_downscale)
         near, far = views.image_near_far(scene, w2c, scene_origin, scene_radius)
         cam = views.Camera(K, c2w, w, h, near, far)
         im = scene["images"][image_id]
-        kp = image_keypoints(im["xys"], im["point3d_ids"], xyz_table, err_table, w, h, img_downscale)
-        rays, rgbs = build_image(cam, img, image_id, kp, w2c, lab, hit, rng, voxel_size, depth_percent, gen, device)
+        kp = image_keypoints(im["xys"], im["point3d_ids"], sc["xyz_table"], sc["err_table"], w, h, img_downscale)
+        yield cam, img, image_id, kp, w2c, lab
+
+
+def build_cache(root_dir, cache_dir="cache", img_downscale=1, semantic_map_path=None, split_to_chunks=-1, sfm_path=None, seed=0,
+                device=None, cache_type="npz", depth_percent=None, use_voxel=True, scene_origin=None, scene_radius=None,
+                stats=None):
+    """tools/prepare_data/prepare_data_cache.py for the training images (`split != "test"`) of the scene at root_dir: writes
+    <root_dir>/<cache_dir>/splits/split_i/{rays,rgbs}N.npz + {rays,rgbs}N_meta_info.json (split_to_chunks > 0) or one
+    raysN.npz / rgbsN.npz.  Returns the files written.
+      * sfm_path: the COLMAP model under dense/ (None: the reference's per-scene choice, views.reference_sfm_path);
+      * semantic_map_path: directory (under root_dir) of the per-image label maps; None = 12-column rows without labels;
+      * depth_percent: None = the reference's per-scene value (`DEPTH_PERCENT`, else 0);
+      * use_voxel: near / far and the ray selection from the two SfM octrees of config.yaml (the reference's default);
+      * seed: every random draw (depth padding per image, chunk padding) comes from generators seeded with it;
+      * stats: an optional dict that receives timings (host decode, device, device -> host bytes, file writing)."""
+    if cache_type != "npz":
+        raise NotImplementedError("cache_type %r: only npz is written (h5py is not a dependency, and raycache.RayCache and the "
+                                  "reference's config/defaults.py read npz); pass cache_type='npz'" % (cache_type,))
+    sc = open_scene(root_dir, img_downscale, sfm_path, device, depth_percent, use_voxel)
+    root_dir, img_downscale, device, scene = sc["root_dir"], sc["img_downscale"], sc["device"], sc["scene"]
+    gen = torch.Generator().manual_seed(int(seed))
+    all_rays, all_rgbs = [], []
+    st = {"n_images": 0, "n_pixels": 0, "n_rays": 0, "d2h_bytes": 0, "t_decode": 0.0, "t_device": 0.0, "t_write": 0.0}
+    t_loop = time.perf_counter()
+    for cam, img, image_id, kp, w2c, lab in scene_items(sc, semantic_map_path, scene_origin, scene_radius, st):
+        rays, rgbs = build_image(cam, img, image_id, kp, w2c, lab, sc["hit"], sc["range"], sc["voxel_size"], sc["depth_percent"], gen,
+                                 device)
         all_rays.append(rays.cpu())
         all_rgbs.append(rgbs.cpu())
-        t2 = time.perf_counter()
         st["n_images"] += 1
-        st["n_pixels"] += w * h
+        st["n_pixels"] += cam.width * cam.height
         st["n_rays"] += int(rays.shape[0])
         st["d2h_bytes"] += 4 * (rays.numel() + rgbs.numel())
-        st["t_decode"] += t1 - t0
-        st["t_device"] += t2 - t1
+    st["t_device"] = time.perf_counter() - t_loop - st["t_decode"]  # everything in the loop that is not the host decode
     if not all_rays:
         raise ValueError("%s lists no training image registered in images.bin" % scene["tsv"])
     t0 = time.perf_counter()

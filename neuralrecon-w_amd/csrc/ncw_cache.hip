@@ -11,8 +11,7 @@
 // Per-pixel kernels: memory- and walk-bound, no MFMA.  No float atomics: bitwise reproducible run to run.
 #include "../../include/neuconw_hip.h"
 #include "ncw_common.h"
-#include "ncw_dda.h"
-#include "ncw_raymath.h"
+#include "ncw_rowmath.h"
 
 #include <math.h>
 
@@ -92,10 +91,8 @@ __global__ __launch_bounds__(CB) void cache_rows_kernel(RowArgs a) {
     if (i < a.n) {
         const int64_t p = a.p0 + i;
         const int row = (int)(p / a.cam.width), col = (int)(p - (int64_t)row * a.cam.width);
-        float d[3];
-        const float nrm = view_ray_dir(a.cam, row, col, d);
-        const float o[3] = {a.cam.c2w[3], a.cam.c2w[7], a.cam.c2w[11]};
-        const float dn[3] = {d[0] / nrm, d[1] / nrm, d[2] / nrm};
+        float o[3], dn[3];
+        row_ray(a.cam, row, col, o, dn);  // ncw_rowmath.h: shared with ncw_source.hip
         float near = a.cam.near, far = a.cam.far;
         bool kept = true;
         if (a.use_voxel) {
@@ -103,12 +100,7 @@ __global__ __launch_bounds__(CB) void cache_rows_kernel(RowArgs a) {
             float hn, hf;
             ray_voxel_near_far(o, dn, a.hit, hn, hf);
             kept = hn > 0.f;
-            if (kept) {
-                float rn, rf;
-                ray_voxel_near_far(o, dn, a.range, rn, rf);
-                near = rn;                                  // 0 / 0 where the range octree misses (:653-654)
-                far = rn > 0.f ? rf + a.voxel_size : rf;    // :305-308
-            }
+            if (kept) row_range_near_far(o, dn, a.range, a.voxel_size, near, far);
         }
         // key-point depth along the ray: z * |((col - cx) / fx, (row - cy) / fy, 1)| -- the reference's dir_norm (a rotation keeps
         // the norm).  Only the few key-point pixels take the f64 branch.
@@ -137,9 +129,9 @@ __global__ __launch_bounds__(CB) void cache_rows_kernel(RowArgs a) {
         r[c + 1] = a.weight[p];
         r[c + 2] = 0.f;  // the column the training batch carries but nothing reads (ncw_batch_assemble: rays[:, 10])
         const uint8_t* px = a.image + 3 * p;
-        s_rgb[3 * threadIdx.x] = (float)px[0] / 255.f;  // torchvision ToTensor: value / 255
-        s_rgb[3 * threadIdx.x + 1] = (float)px[1] / 255.f;
-        s_rgb[3 * threadIdx.x + 2] = (float)px[2] / 255.f;
+        s_rgb[3 * threadIdx.x] = row_rgb(px[0]);
+        s_rgb[3 * threadIdx.x + 1] = row_rgb(px[1]);
+        s_rgb[3 * threadIdx.x + 2] = row_rgb(px[2]);
         a.keep[i] = kept ? 1 : 0;
     }
     __syncthreads();

@@ -58,6 +58,19 @@ def _read_chunk(stem, cache_type, key):
         return np.asarray(f[key][:])
 
 
+def shuffled_epoch(source, batch_size, generator=None, drop_last=False, max_batches=None, skip_batches=0):
+    """The epoch loop `RayCache` and `raysource.RaySource` share: one `torch.randperm(len(source))` on the source's device,
+    then `source.batch` of its consecutive slices (see `RayCache.epoch`)."""
+    n = len(source)
+    perm = torch.randperm(n, device=source.device, generator=generator)
+    for i, s in enumerate(range(0, n, batch_size)):
+        if (drop_last and s + batch_size > n) or (max_batches is not None and i >= max_batches):
+            return
+        if i < skip_batches:
+            continue
+        yield source.batch(perm[s:s + batch_size])
+
+
 class RayCache:
     """The rank's training rays, resident on `device`.
 
@@ -135,11 +148,4 @@ class RayCache:
         max_batches: stop after that many (every rank of a data-parallel job must run the same number of steps);
         skip_batches: a resumed run drops the batches the interrupted epoch already consumed (same permutation when the
         generator is restored to its state at the start of that epoch)."""
-        n = len(self)
-        perm = torch.randperm(n, device=self.device, generator=generator)
-        for i, s in enumerate(range(0, n, batch_size)):
-            if (drop_last and s + batch_size > n) or (max_batches is not None and i >= max_batches):
-                return
-            if i < skip_batches:
-                continue
-            yield self.batch(perm[s:s + batch_size])
+        return shuffled_epoch(self, batch_size, generator, drop_last, max_batches, skip_batches)

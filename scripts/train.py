@@ -7,6 +7,8 @@
   * experiment yaml + scene config.yaml as the reference reads them (neuralrecon_w_amd.config);
   * this rank's share of the npz ray-cache chunks (datasets/data.py:83-119) uploaded to HBM once, batches assembled on
     the device, black-listed labels (RAY_MASK_LIST) removed once at load time -> fixed-size, sync-free steps;
+  * --ray_source scene (opt-in): no cache files -- the scene's images, COLMAP model and label maps become 8-byte records on the
+    device and every batch's rows are rebuilt by one launch (neuralrecon_w_amd.raysource); same rows, same steps;
   * Adam(eps 1e-7), lr = CANONICAL_LR * world * batch / CANONICAL_BS, grad-norm clip 0.99, ONE flat RCCL all-reduce;
   * cos_anneal_ratio = min(1, step / ANNEAL_END); every UPDATE_FREQ steps the fine octree is rebuilt from the current SDF
     (coarse octree from the COLMAP points: voxel.octree_from_sfm); checkpoints every SAVE_FREQ steps in the reference's
@@ -109,11 +111,30 @@ def build_parser():
     ap.add_argument("--val_sfm_path", default=None,
                     help="COLMAP model of --val_every under <root_dir>/dense/ -- the one the ray cache was built from (default: the "
                          "reference's per-scene choice, ../neuralsfm for brandenburg_gate and palacio_de_bellas_artes, else sparse)")
+    ap.add_argument("--ray_source", default="cache", choices=["cache", "scene"],
+                    help="cache: the npz ray cache under DATASET.PHOTOTOURISM.CACHE_DIR (scripts/prepare_data_cache.py); scene: no cache -- rays are "
+                         "rebuilt per batch on the GPU from the scene directory itself (neuralrecon_w_amd.raysource)")
+    ap.add_argument("--semantic_map_path", default=None,
+                    help="--ray_source scene: directory of the label maps under the scene (default: DATASET.PHOTOTOURISM."
+                         "SEMANTIC_MAP_PATH, 'semantic_maps', when the config has WITH_SEMANTICS)")
+    ap.add_argument("--sfm_path", default=None,
+                    help="--ray_source scene: COLMAP model under <root_dir>/dense/ (default: the reference's per-scene choice)")
+    ap.add_argument("--depth_percent", type=float, default=None,
+                    help="--ray_source scene: share of rays with a key-point depth each image is padded up to (default: the "
+                         "reference's per-scene value)")
+    ap.add_argument("--source_seed", type=int, default=0, help="--ray_source scene: seed of the depth_percent padding draws")
     return ap
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.ckpt_path:
+        # the interrupted epoch's permutation indexes the rows of the source it was drawn for; the other source holds another
+        # row set in another order.  Checked before anything is built.
+        kind = (torch.load(args.ckpt_path, map_location="cpu").get("ncw_resume") or {}).get("ray_source", "cache")
+        if kind != args.ray_source:
+            raise SystemExit("%s was written with --ray_source %s: resuming it with --ray_source %s would permute a different set "
+                             "of rays; pass --ray_source %s" % (args.ckpt_path, kind, args.ray_source, kind))
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if os.environ.get("NCW_TRAIN_ONE_GPU_TEST"):  # plumbing test: the ranks share GPU 0 (collectives over gloo)
@@ -136,9 +157,20 @@ def main(argv=None):
     rdr.sync_free = True
     n, pt = cfg["NEUCONW"], cfg["DATASET"]["PHOTOTOURISM"]
     root = cfg["DATASET"]["ROOT_DIR"]
-    names = raycache.local_splits(raycache.list_splits(root, pt["CACHE_DIR"]), world, rank)
-    cache = raycache.RayCache(root, pt["CACHE_DIR"], names, dev, img_downscale=pt["IMG_DOWNSCALE"],
-                              with_semantics=pt["WITH_SEMANTICS"], ray_mask_list=n["RAY_MASK_LIST"], prefilter=True)
+    if args.ray_source == "scene":
+        from neuralrecon_w_amd import raysource
+
+        sem_path = args.semantic_map_path
+        if sem_path is None and pt["WITH_SEMANTICS"]:
+            sem_path = pt.get("SEMANTIC_MAP_PATH") or "semantic_maps"
+        cache = raysource.RaySource.from_scene(root, img_downscale=pt["IMG_DOWNSCALE"], semantic_map_path=sem_path,
+                                               sfm_path=args.sfm_path, seed=args.source_seed, depth_percent=args.depth_percent,
+                                               ray_mask_list=n["RAY_MASK_LIST"], prefilter=True, world_size=world, rank=rank,
+                                               device=dev)
+    else:
+        names = raycache.local_splits(raycache.list_splits(root, pt["CACHE_DIR"]), world, rank)
+        cache = raycache.RayCache(root, pt["CACHE_DIR"], names, dev, img_downscale=pt["IMG_DOWNSCALE"],
+                                  with_semantics=pt["WITH_SEMANTICS"], ray_mask_list=n["RAY_MASK_LIST"], prefilter=True)
     # Every rank runs the SAME number of steps per epoch: with the black-listed rays removed at load time the ranks'
     # caches differ in length, and a rank that leaves the loop early would strand the others in the gradient all-reduce
     # (the reference pads its chunks to equal length and filters inside the batch: datasets/data.py:83-119).
@@ -149,7 +181,10 @@ def main(argv=None):
         steps_per_epoch = int(t.item())
     if steps_per_epoch < 1:
         raise SystemExit("a rank holds fewer than --batch_size rays (%d)" % len(cache))
-    if rank == 0:
+    if rank == 0 and args.ray_source == "scene":
+        print("[rank 0] ray source: scene (%d images), %d rays resident on %s at %.2f B/ray; %d steps/epoch; lr %.3g"
+              % (cache.n_img, len(cache), dev, cache.nbytes() / max(1, len(cache)), steps_per_epoch, lr))
+    elif rank == 0:
         print("[rank 0] %d cache chunk(s), %d rays resident on %s; %d steps/epoch; lr %.3g"
               % (len(names), len(cache), dev, steps_per_epoch, lr))
     step_fn = nw.TrainStep(rdr, [emb, neuconw, nerf], C.neuconw_loss(cfg), lr=lr, eps=1e-7, clip=0.99, world_size=world)
@@ -196,6 +231,11 @@ def main(argv=None):
         cur = C.lr_at_epoch(cfg, lr, epoch_, args.num_epochs)
         return {"last_epoch": int(epoch_), "_step_count": int(epoch_) + 1, "_last_lr": [cur], "base_lrs": [lr], "kind": sched_kind}
 
+    def resume_extra(epoch_, in_epoch_, gstate_):
+        st = trainer.resume_state(step_fn.opt, rdr, epoch_, in_epoch_, gstate_)
+        st["ray_source"] = args.ray_source
+        return {"ncw_resume": st}
+
     # bound before the loop: a checkpoint whose epoch is already >= --num_epochs (or a loop whose body never runs) still
     # writes last.ckpt below
     epoch, in_epoch, gen_state0 = first_epoch, skip, gen.get_state()
@@ -222,7 +262,7 @@ def main(argv=None):
                 os.makedirs(save_dir, exist_ok=True)
                 trainer.save_checkpoint(os.path.join(save_dir, "iter_%d.ckpt" % step), emb, neuconw, nerf,
                                         optimizer=step_fn.opt, global_step=step + 1, epoch=epoch, lr_scheduler=sched_state(epoch),
-                                        extra={"ncw_resume": trainer.resume_state(step_fn.opt, rdr, epoch, in_epoch, gen_state0)})
+                                        extra=resume_extra(epoch, in_epoch, gen_state0))
             if rank == 0 and step % args.log_every == 0:
                 now = time.perf_counter()
                 gn = float(getattr(step_fn, "last_grad_norm", float("nan")))
@@ -248,7 +288,7 @@ def main(argv=None):
         os.makedirs(save_dir, exist_ok=True)
         trainer.save_checkpoint(os.path.join(save_dir, "last.ckpt"), emb, neuconw, nerf, optimizer=step_fn.opt, global_step=step,
                                 epoch=epoch, lr_scheduler=sched_state(epoch),
-                                extra={"ncw_resume": trainer.resume_state(step_fn.opt, rdr, epoch, in_epoch, gen_state0)})
+                                extra=resume_extra(epoch, in_epoch, gen_state0))
         print("%d steps in %.1f s; wrote %s" % (step, time.perf_counter() - t0, os.path.join(save_dir, "last.ckpt")))
     print("[rank %d] finished after %d steps with %d rays resident" % (rank, step, len(cache)))
     if world > 1:
