@@ -1156,6 +1156,74 @@ int ncw_mesh_compact_mark(const int32_t* faces, const uint8_t* keep, int64_t n_f
 int ncw_mesh_compact_faces(const int32_t* faces, const uint8_t* keep, const int32_t* face_offset, const int32_t* vmap,
                            int64_t n_faces, int64_t n_verts, int64_t n_out, int32_t* faces_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Mesh simplification (csrc/ncw_simplify.hip; meshops.simplify): uniform-grid vertex clustering with a quadric-optimal
+ * representative per cell (Lindstrom, out-of-core simplification).  THE REFERENCE HAS NO SUCH MODE (it leaves decimation to an
+ * external tool): the rules below are this project's, and no parity with open3d's simplify_vertex_clustering, trimesh or
+ * meshlab is claimed.  Restated in numpy by tests/_simplify_ref.py.
+ * verts [V,3] float64 (float32 input is converted exactly by the caller), faces [F,3] int32, cell size h > 0 (float64),
+ * eps (default 1e-3).  ALL ARITHMETIC IS FLOAT64, EVERY PRODUCT, SUM AND QUOTIENT ROUNDED ON ITS OWN (no fused multiply-add),
+ * every sum sequential in the stated order, one lane per sum.  No float atomics: bitwise reproducible.
+ *  1 PARTICIPATION  A face takes part iff its corners lie in [0, V) and are pairwise distinct (ncw_mesh_face_select's rule).
+ *                   A vertex is USED iff a participating face names it (ncw_mesh_compact_mark of those faces).
+ *  2 GRID           lo, hi = componentwise min / max over the used vertices (caller, exact).  n = floor((hi - lo) / h) + 1 per
+ *                   axis.  Cell index i = clamp(floor((x - lo) / h), 0, n - 1) per axis -- a division, so a coordinate with
+ *                   x - lo = k h exactly goes to the upper cell k.  key = (i_x n_y + i_y) n_z + i_z, int64.  The caller refuses
+ *                   n_x n_y n_z >= 2^62, h not finite and positive, non-finite lo / hi, and a mesh with no participating face.
+ *                   Cell centre c = lo + (i + 0.5) h  (i + 0.5 exact, then the product, then the sum).
+ *  3 CLUSTERS       The distinct keys of used vertices in ascending order, numbered 0 .. C-1 (caller).  cluster [V] int32 holds
+ *                   the number of a used vertex and -1 for an unused one.
+ *  4 MEMBER MEAN    m_k = (sum of (x_v - c_k) over the used vertices of cluster k in ascending v, from 0.0) / count.
+ *  5 QUADRIC        A participating face contributes to cluster k ONCE per distinct cluster among its corners: corner j
+ *                   contributes iff its cluster differs from the clusters of the corners before it.  With P_i = x_i - c_k for
+ *                   the face's corners i = 0, 1, 2 in the face's own order:
+ *                       u = P_1 - P_0, w = P_2 - P_0, n = u x w = (u_y w_z - u_z w_y, u_z w_x - u_x w_z, u_x w_y - u_y w_x),
+ *                       d = (n_x P_0x + n_y P_0y) + n_z P_0z,
+ *                       A_00 += n_x n_x, A_01 += n_x n_y, A_02 += n_x n_z, A_11 += n_y n_y, A_12 += n_y n_z, A_22 += n_z n_z,
+ *                       b += d n,
+ *                   from 0.0, over the cluster's faces in ascending face index.  A zero-area face adds zeros.
+ *  6 PLACEMENT      t = (A_00 + A_11) + A_22.  t == 0: p = m.  Otherwise lam = (eps t) / 3, M = A + lam I, r = b + lam m and
+ *                   p = M^-1 r by cofactors, in this order:
+ *                       c00 = M11 M22 - M12 M12,  c01 = M02 M12 - M01 M22,  c02 = M01 M12 - M02 M11,
+ *                       c11 = M00 M22 - M02 M02,  c12 = M01 M02 - M00 M12,  c22 = M00 M11 - M01 M01,
+ *                       det = (M00 c00 + M01 c01) + M02 c02,
+ *                       p_0 = ((c00 r_0 + c01 r_1) + c02 r_2) / det,  p_1 = ((c01 r_0 + c11 r_1) + c12 r_2) / det,
+ *                       p_2 = ((c02 r_0 + c12 r_1) + c22 r_2) / det.
+ *                   If det is not finite or not > 0, or some |p_i| <= h / 2 does not hold (p outside the cell, or NaN): p = m.
+ *                   Output vertex c_k + p; at_mean[k] = 1 iff p = m was taken (t == 0 included).
+ *  7 FACES          A participating face SURVIVES iff its three clusters are distinct.  It is rotated, not reflected, so that
+ *                   its smallest cluster comes first.  Survivors with equal rotated triples are duplicates and the one with the
+ *                   smallest input index is kept (caller: stable sorts); a pair of OPPOSITE orientation is not a duplicate,
+ *                   both stay.  Output faces in ascending input index.
+ *  8 OUTPUT         Only the clusters some kept face names, ascending (caller: meshops.submesh).  All faces collapsing gives
+ *                   the empty mesh.
+ *  9 COLOURS        (optional, uint8 [V,3]) per cluster and channel floor(sum / count + 0.5) over its used members; integer
+ *                   sums, computed as (2 sum + count) / (2 count) in integers.
+ * Clustering can create non-manifold edges and joins components that come within one cell of each other.
+ *   ncw_mesh_sc_keys  : keys [V] int64 = the key of every vertex with used[v] != 0, -1 elsewhere.  lo [3] and n [3] are HOST
+ *                       pointers.
+ *   ncw_mesh_sc_faces : per face: tri [F,3] int32 = the rotated cluster triple of a survivor, (-1, -1, -1) otherwise;
+ *                       survive [F] uint8; inc [F,3] int32 = per corner the cluster the face contributes to (rule 5), -1
+ *                       where it does not (every corner of a face that takes no part).
+ *   (caller)          : CSR per cluster by stable sorts: mem [n_mem] int32 = the used vertices by cluster, ascending v within
+ *                       one; inc [n_inc] int32 = the FACE index of the inc entries >= 0 by cluster, ascending face within one;
+ *                       mem_off / inc_off [C+1] int64; keys [C] int64 = the cluster's key.
+ *   ncw_mesh_sc_place : one lane per cluster, rules 4, 5, 6, 9: out_verts [C,3] float64, at_mean [C] uint8, out_colors [C,3]
+ *                       uint8 (colors and out_colors both or neither).  List entries outside [0, V) / [0, F), faces that take
+ *                       no part and offsets outside the lists are skipped, never used as indices.
+ * All return NCW_E_BADARG without a launch for a missing pointer, counts outside their ranges (V, F <= 2^31 - 1, C <= V,
+ * n_mem <= V, n_inc <= 3 F), a grid the caller must refuse (above; n < 1), eps negative or not finite; 0 without a launch for an
+ * empty range.
+ * ---------------------------------------------------------------------------------------- */
+int ncw_mesh_sc_keys(const double* verts, const uint8_t* used, int64_t n_verts, const double* lo, double h, const int64_t* n,
+                     int64_t* keys, void* stream);
+int ncw_mesh_sc_faces(const int32_t* faces, int64_t n_faces, int64_t n_verts, const int32_t* cluster, int64_t n_clusters,
+                      int32_t* tri, uint8_t* survive, int32_t* inc, void* stream);
+int ncw_mesh_sc_place(const double* verts, const int32_t* faces, int64_t n_verts, int64_t n_faces, const int64_t* keys,
+                      int64_t n_clusters, const int64_t* mem_off, const int32_t* mem, int64_t n_mem, const int64_t* inc_off,
+                      const int32_t* inc, int64_t n_inc, const double* lo, double h, const int64_t* n, double eps,
+                      const uint8_t* colors, double* out_verts, uint8_t* at_mean, uint8_t* out_colors, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

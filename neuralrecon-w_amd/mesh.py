@@ -136,7 +136,7 @@ def sparse_volume(sparse_data, sdf_values):
 @torch.no_grad()
 def extract_mesh(renderer, dim, scene_radius, scene_origin, origin=None, radius=1.0, with_color=False, embedding_a=None,
                  level=0.0, chunk_rgb=1 << 16, sparse_data=None, chunk=1 << 22, group=None, min_component_faces=0,
-                 largest_components=None):
+                 largest_components=None, simplify_cells=0):
     """utils/visualization.py:37-159.  Dense path: the [dim]^3 lattice over `origin` +- `radius` (training coordinates), swept
     on chip and sharded over the ranks (grid.sdf_grid).  Sparse path (`sparse_data` from gen_grid_spc): the SDF only at the
     sub-voxels of the occupied octree voxels (sharded like neuconw_system.py:236-256), marching cubes under the all-8-corners
@@ -144,7 +144,10 @@ def extract_mesh(renderer, dim, scene_radius, scene_origin, origin=None, radius=
     tensors, on every rank (the reference returns the mesh on rank 0 only).
     min_component_faces > 0 / largest_components = K (not in the reference; both off: this path is not taken): after marching
     cubes and BEFORE the colour pass, only the connected components (by shared vertex index, meshops.clean) of at least that
-    many faces / the K with the most faces are kept, so the colour network never runs on floaters."""
+    many faces / the K with the most faces are kept, so the colour network never runs on floaters.
+    simplify_cells > 0 (not in the reference; 0: this path is not taken): after that clean-up and before the colour pass,
+    meshops.simplify with a cell of `simplify_cells` voxels (grid-index units): vertex clustering with a quadric-optimal vertex
+    per cell, so the colour network runs on far fewer vertices."""
     dev = next(renderer.neuconw.parameters()).device
     so = torch.as_tensor(np.asarray(scene_origin, dtype=np.float32), device=dev).reshape(3)
     if sparse_data is None:
@@ -170,6 +173,11 @@ def extract_mesh(renderer, dim, scene_radius, scene_origin, origin=None, radius=
         from . import meshops
 
         verts, faces, _, _ = meshops.clean(verts, faces, None, min_component_faces, largest_components)
+        faces = faces.long()
+    if float(simplify_cells) > 0 and faces.shape[0] > 0:
+        from . import meshops
+
+        verts, faces, _, _ = meshops.simplify(verts, faces, float(simplify_cells))
         faces = faces.long()
     verts_t = verts * voxel_size + vol_origin                                    # :116
     verts_w = verts_t * float(scene_radius) + so                                 # :117

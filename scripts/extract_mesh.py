@@ -15,7 +15,10 @@ kaolin, skimage or trimesh -- one process per GPU.
     binary PLY on the GPU of rank 0 (mesh.py); file name and directory follow :112-114,160-167;
   * --min_component_faces N / --largest_components K (not in the reference): after marching cubes and BEFORE the colour pass,
     drop the connected components (by shared vertex, meshops.py) of fewer than N faces / keep the K with the most faces; the
-    file name is unchanged.
+    file name is unchanged;
+  * --simplify_cells K (not in the reference; 0 = off): after that clean-up and BEFORE the colour pass, vertex clustering on a
+    grid of K voxels per cell with a quadric-optimal vertex per cell (meshops.simplify): far fewer vertices for the colour
+    network and a far smaller file; the file name is unchanged.
 """
 import argparse
 import os
@@ -46,6 +49,7 @@ def main():
     ap.add_argument("--out_dir", default=None, help="default: results/<dataset_name>/<ckpt dir>_<ckpt name>/mesh")
     ap.add_argument("--min_component_faces", type=int, default=0, help="drop connected components of fewer faces (floaters)")
     ap.add_argument("--largest_components", type=int, default=None, help="keep the K components with the most faces")
+    ap.add_argument("--simplify_cells", type=float, default=0, help="simplify by vertex clustering, cell size in voxels (0 = off)")
     ap.add_argument("--prec", default=None, choices=["bf16", "f16", "f32"], help="default: fp32 for the colour pass, SDFNetwork.value_prec() for the SDF lattice")
     args = ap.parse_args()
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
@@ -81,7 +85,7 @@ def main():
     m = mesh.extract_mesh(rdr, args.mesh_size, scene["radius"], scene["origin"], origin=origin, radius=args.mesh_radius,
                           with_color=args.vertex_color, embedding_a=a, chunk_rgb=args.chunk_rgb, sparse_data=sparse,
                           chunk=args.chunk, min_component_faces=args.min_component_faces,
-                          largest_components=args.largest_components)
+                          largest_components=args.largest_components, simplify_cells=args.simplify_cells)
     if rank == 0:
         save_name = "_".join(os.path.normpath(args.ckpt_path).split(os.sep)[-2:]).replace(".ckpt", "")
         out_dir = args.out_dir or os.path.join("results", args.dataset_name, save_name, "mesh")
