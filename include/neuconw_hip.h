@@ -1224,6 +1224,53 @@ int ncw_mesh_sc_place(const double* verts, const int32_t* faces, int64_t n_verts
                       const int32_t* inc, int64_t n_inc, const double* lo, double h, const int64_t* n, double eps,
                       const uint8_t* colors, double* out_verts, uint8_t* at_mean, uint8_t* out_colors, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Estimating sfm2gt (csrc/ncw_align.hip; align.icp_similarity): the two kernels of a gated point-to-point ICP with a similarity
+ * transform (Umeyama), source = the filtered SfM points P [N,3] float64, target = the ground-truth cloud Q [M,3] float64,
+ * bucketed ONCE by the caller (evalmesh.NNGrid over float32(Q - centre)); the source is transformed every iteration, the target
+ * never.  THE REFERENCE HAS NO SUCH TOOL (heritage-recon ships the matrices): the rules below are this project's, and no parity
+ * with open3d / CloudCompare registration is claimed.  Restated in numpy by tests/_align_ref.py.
+ * ALL ARITHMETIC IS FLOAT64 UNLESS SAID OTHERWISE, EVERY PRODUCT AND SUM ROUNDED ON ITS OWN (no fused multiply-add).  No float
+ * atomics: bitwise reproducible.  T [12]: a 3x4 row-major matrix (rows of sR | t), a HOST pointer, as are centre, box_lo,
+ * box_hi, cp and cq.
+ *  1 TRANSFORM      x_a = ((T[4a] p_x + T[4a+1] p_y) + T[4a+2] p_z) + T[4a+3]   for a = 0, 1, 2.
+ *  2 QUERY          q32_a = (float)(x_a - centre_a): one float64 subtraction, one rounding to float32.
+ *  3 INSIDE         inside = 1 iff for every axis  q32_a >= box_lo_a - gate  and  q32_a <= box_hi_a + gate, the two bounds and the
+ *                   comparisons in float32 (box_lo / box_hi: the target's box, recentred, float32); 0 if a coordinate is NaN.
+ *                   A point that is not inside has no partner within the gate: the caller does not query it and gives it
+ *                   idx = -1.  |q32| of every queried point is at most the box's half-extent plus the gate.
+ *  4 PAIRS          Pair i takes part iff 0 <= idx[i] < M and dist[i] <= gate (float32, inclusive; a NaN dist takes no part).
+ *  5 TERMS          With p = P[i] - cp, q = Q[idx[i]] - cq (componentwise), x = rule 1 of P[i], d = x - Q[idx[i]]:
+ *                       s[0..2] += p_a,   s[3..5] += q_a,   s[6 + 3a + b] += p_a q_b,
+ *                       s[15] += (p_x p_x + p_y p_y) + p_z p_z,   s[16] += (q_x q_x + q_y q_y) + q_z q_z,
+ *                       s[17] += (d_x d_x + d_y d_y) + d_z d_z  (= r2),
+ *                       s[18] += (double)dist[i],   s[19] += (double)dist[i] (double)dist[i],
+ *                   counts[0] += 1 (int64), counts[1] = max(counts[1], bit pattern of r2 as int64) over the pairs whose r2 is
+ *                   not NaN (a non-negative double orders like its bit pattern), from 0.
+ *  6 ORDER          L = NCW_ALIGN_LANES lanes, B = NCW_ALIGN_BLOCK points per block, ceil(N / B) blocks.  Block b, lane l adds
+ *                   the terms of the points b B + j L + l for j = 0, 1, .. B / L - 1 (those below N that take part) in ascending
+ *                   j, each of the 20 sums on its own from 0.0.  LANE TREE: v[l] = v[l] + v[l + s] for s = 32, 16, 8, 4, 2, 1
+ *                   inside every group of 64 consecutive lanes (l mod 64 < s), leaving the group sums w_0 .. w_3 on lanes 0, 64,
+ *                   128, 192; the block's row is (w_0 + w_1) + (w_2 + w_3).  FOLD: one workgroup of L lanes, lane l adds the
+ *                   rows l, l + L, l + 2 L, .. in ascending order from 0.0, then the same lane tree.  The result is a function
+ *                   of N and the data only.
+ *   ncw_align_transform  : rules 1-3 for n points: q32 [n,3] float32, inside [n] uint8.
+ *   ncw_align_sums_blocks: ceil(n / NCW_ALIGN_BLOCK), 0 for n <= 0: the rows of scratch the caller provides.
+ *   ncw_align_sums       : rules 4-6: sums [20] float64, counts [2] int64; scratch part [blocks, 20] float64, ipart [blocks, 2]
+ *                          int64 (both may be NULL when n == 0, as may src / idx / dist).  n == 0 gives zeros.
+ * Both return NCW_E_BADARG without a launch for a missing pointer, n outside [0, 2^31 - 1] or m < 0; ncw_align_transform
+ * returns 0 without a launch for n == 0.
+ * ---------------------------------------------------------------------------------------- */
+#define NCW_ALIGN_LANES 256
+#define NCW_ALIGN_BLOCK 1024
+#define NCW_ALIGN_SUMS 20
+int ncw_align_transform(const double* src, int64_t n, const double* T, const double* centre, const float* box_lo,
+                        const float* box_hi, float gate, float* q32, uint8_t* inside, void* stream);
+int64_t ncw_align_sums_blocks(int64_t n);
+int ncw_align_sums(const double* src, int64_t n, const double* cp, const double* dst, int64_t m, const double* cq,
+                   const int64_t* idx, const float* dist, float gate, const double* T, double* part, int64_t* ipart,
+                   double* sums, int64_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

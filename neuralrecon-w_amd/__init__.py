@@ -9,7 +9,7 @@ torch.  `import neuralrecon_w_amd` alone therefore loads nothing: a missing modu
 """
 import importlib
 
-_SUBMODULES = ("lib", "mesh", "evalmesh", "reproj", "views", "appfit")
+_SUBMODULES = ("lib", "mesh", "evalmesh", "reproj", "views", "appfit", "align")
 _HOME = {"PREC_BF16": "lib", "PREC_F16": "lib", "PREC_F32": "lib", "NeuconwHipError": "lib", "NeRF": "nerf", "NeuconW": "neuconw",
          "RenderingNetwork": "neuconw", "SDFNetwork": "neuconw", "SingleVarianceNetwork": "neuconw", "NeuconWRenderer": "renderer",
          "NeuconWLoss": "losses", "FlatAdam": "trainer", "FlatParams": "trainer", "TrainStep": "trainer", "Camera": "views",

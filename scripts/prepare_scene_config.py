@@ -4,7 +4,8 @@ tools/pre_process.py (:35-46, 102-108, 135-158; see neuralrecon_w_amd/sceneprep.
     python scripts/prepare_scene_config.py --root_dir data/my_scene [--name my_scene] [--sfm_path sparse] [--overwrite]
 
 The box is the 4th .. 96th percentile per axis of the points with more than 2 observations; origin its centre, radius its
-longest edge.  sfm2gt is the identity: a scene with ground truth replaces it (and eval_bbx) by hand, as the reference's do.
+longest edge.  sfm2gt is the identity: a scene with ground truth replaces it with scripts/estimate_sfm2gt.py (which also suggests
+an eval_bbx; the reference's scenes ship both).
 The folder regrouping and COLMAP's image undistorter of pre_process.py are not part of this tool.  No GPU is needed."""
 import argparse
 import os
