@@ -627,6 +627,39 @@ int ncw_mc_emit(const float* sdf, const uint8_t* mask, int Dx, int Dy, int Dz, f
                 const int32_t* ntri, const int32_t* edges, const int64_t* offsets, float* tri_pos, int64_t* tri_key,
                 void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Marching cubes on brick-blocked sparse values (csrc/ncw_mc_sparse.hip; mesh.isosurface_sparse): the same surface as
+ * ncw_mc_count / ncw_mc_emit under the all-8-corners mask of the sparse mode, without any array of the size of the lattice.
+ *   bricks [n,3] int32: the occupied coarse voxels of a [G]^3 lattice, STRICTLY ASCENDING lexicographically in (x, y, z) and
+ *                       inside [0, G) (device data: the caller's contract, mesh.isosurface_sparse checks it; whatever the
+ *                       list holds, no kernel reads or writes outside its arrays);
+ *   up                : sub-voxels per side of a brick, a power of two in 1..32; the fine lattice has side D = G * up <= 16384;
+ *   values [K] f32    : K = n * up^3 <= 2^31 - 1, brick-major, then local x, y, z with z fastest (gen_grid_spc's order).
+ * A cube is used iff all 8 of its corners are among the K points; corners across an upper face of a brick come from the up to
+ * 7 upper neighbour bricks.  Shared with the dense path (csrc/ncw_mc.h): the cube, the configuration test and the edge
+ * interpolation, so a vertex has the same bits on both.
+ *   ncw_mcs_neighbors: nbr [n,7] int32: entry o - 1 (o = 1..7; bit0 = +x, bit1 = +y, bit2 = +z) = index of the brick at that
+ *                      offset, -1 where it is absent or outside the lattice (binary search in the ascending list).
+ *   ncw_mcs_count    : counts [K] uint8 = triangles (0..5) of the cube whose minimum corner is sub-voxel i, 0 for an unused cube.
+ *   ncw_mcs_cube_ids : sub [M] int64 = indices into counts (the caller's compaction of the non-empty cubes);
+ *                      ids [M] int64 = global grid point id (x * D + y) * D + z of each cube's minimum corner.  Sorting by it
+ *                      gives the dense path's cube order (x slowest).
+ *   ncw_mcs_emit     : sub [M] in that order, offsets [M] int64 = EXCLUSIVE prefix sum of their counts, T = the total; writes
+ *                      tri_pos [T,3,3] f32 in fine grid-index coordinates and tri_key [T,3] int64 = lo_point * 3 + a (a = 0, 1, 2
+ *                      for the edge along z, y, x): it sorts as the dense key lo_point * n_points + hi_point does and cannot
+ *                      overflow.  Winding as ncw_mc_emit.  One lane per output element, no atomics: bitwise reproducible.
+ * All return NCW_E_BADARG without a launch for up not a power of two in 1..32, n < 0, K > 2^31 - 1, n_values != K, G < 1,
+ * G * up > 16384 (ncw_mcs_neighbors: G > 16384, n > 2^31 - 1), M outside [0, K], T outside [0, 5 M] or a missing pointer; 0
+ * without a launch for n == 0 (neighbors, count) or M == 0 (cube_ids, emit).
+ * ---------------------------------------------------------------------------------------- */
+int ncw_mcs_neighbors(const int32_t* bricks, int64_t n, int G, int32_t* nbr, void* stream);
+int ncw_mcs_count(const float* values, int64_t n_values, const int32_t* bricks, const int32_t* nbr, int64_t n, int up, int G,
+                  float level, const int32_t* ntri, uint8_t* counts, void* stream);
+int ncw_mcs_cube_ids(const int32_t* bricks, int64_t n, int up, int G, const int64_t* sub, int64_t M, int64_t* ids, void* stream);
+int ncw_mcs_emit(const float* values, int64_t n_values, const int32_t* bricks, const int32_t* nbr, int64_t n, int up, int G,
+                 float level, const int8_t* tri, const int32_t* ntri, const int32_t* edges, const int64_t* sub,
+                 const int64_t* offsets, int64_t M, int64_t T, float* tri_pos, int64_t* tri_key, void* stream);
+
 
 /* ------------------------------------------------------------------------------------------
  * Exact 1-nearest-neighbour search for the mesh evaluation: replaces the per-point

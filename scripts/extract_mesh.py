@@ -18,7 +18,11 @@ kaolin, skimage or trimesh -- one process per GPU.
     file name is unchanged;
   * --simplify_cells K (not in the reference; 0 = off): after that clean-up and BEFORE the colour pass, vertex clustering on a
     grid of K voxels per cell with a quadric-optimal vertex per cell (meshops.simplify): far fewer vertices for the colour
-    network and a far smaller file; the file name is unchanged.
+    network and a far smaller file; the file name is unchanged;
+  * --sparse_mc {auto,dense,bricks} (not in the reference; --eval_level > 0 only): `dense` scatters the sparse SDF into the
+    [dim]^3 lattice first (what the reference does; stops at level 10, dim 1024), `bricks` runs marching cubes on the values as
+    they are blocked by octree voxel (mesh.isosurface_sparse: no lattice, levels up to dim 16384, the same mesh bit for bit),
+    `auto` (default) takes `dense` up to dim 1024 and `bricks` above.
 """
 import argparse
 import os
@@ -33,7 +37,7 @@ from neuralrecon_w_amd import config as C  # noqa: E402
 from neuralrecon_w_amd import mesh, trainer, voxel  # noqa: E402
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--cfg_path", required=True, help="config path")
     ap.add_argument("--root_dir", default=None, help="overrides DATASET.ROOT_DIR")
@@ -50,8 +54,14 @@ def main():
     ap.add_argument("--min_component_faces", type=int, default=0, help="drop connected components of fewer faces (floaters)")
     ap.add_argument("--largest_components", type=int, default=None, help="keep the K components with the most faces")
     ap.add_argument("--simplify_cells", type=float, default=0, help="simplify by vertex clustering, cell size in voxels (0 = off)")
+    ap.add_argument("--sparse_mc", default="auto", choices=["auto", "dense", "bricks"],
+                    help="marching cubes of the sparse mode: on the dense lattice (up to level 10), on the octree bricks, or auto")
     ap.add_argument("--prec", default=None, choices=["bf16", "f16", "f32"], help="default: fp32 for the colour pass, SDFNetwork.value_prec() for the SDF lattice")
-    args = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     if os.environ.get("NCW_TRAIN_ONE_GPU_TEST"):  # plumbing test: the ranks share GPU 0 (collectives over gloo)
@@ -85,7 +95,8 @@ def main():
     m = mesh.extract_mesh(rdr, args.mesh_size, scene["radius"], scene["origin"], origin=origin, radius=args.mesh_radius,
                           with_color=args.vertex_color, embedding_a=a, chunk_rgb=args.chunk_rgb, sparse_data=sparse,
                           chunk=args.chunk, min_component_faces=args.min_component_faces,
-                          largest_components=args.largest_components, simplify_cells=args.simplify_cells)
+                          largest_components=args.largest_components, simplify_cells=args.simplify_cells,
+                          sparse_mc=args.sparse_mc)
     if rank == 0:
         save_name = "_".join(os.path.normpath(args.ckpt_path).split(os.sep)[-2:]).replace(".ckpt", "")
         out_dir = args.out_dir or os.path.join("results", args.dataset_name, save_name, "mesh")
