@@ -680,6 +680,27 @@ int ncw_mcs_emit(const float* values, int64_t n_values, const int32_t* bricks, c
  *                       or when the block covers the grid.  Queries still open after `max_shell` shells are appended to
  *                       escaped[] (their count in *n_escaped, zeroed by the caller) and left unwritten.
  *   ncw_nn_brute      : the escaped queries against all of P; scratch uint64[n_esc].
+ * NEAREST POINT WITHIN A RADIUS (one launch per query set: no escape list, no brute-force pass):
+ *   ncw_nn_coarse     : from the cell_range of a built grid, coarse[c0*c1*c2] int32 = the number of points in every block
+ *                       of B^3 fine cells (B a power of two in [1, 65536]; c_a = ceil(dim[a] / B); block (bx, by, bz) at
+ *                       (bx * c1 + by) * c2 + bz).  Integer work only.
+ *   ncw_nn_query_within: the inputs of ncw_nn_query plus that table, B and max_dist.  With r2 = max_dist * max_dist (one
+ *                       float32 product, formed by this entry) and (d2, i) = the minimum of dx*dx + dy*dy + dz*dz over ALL of P
+ *                       with ties to the smaller index: dist = sqrtf(d2), idx = i if d2 <= r2 (inclusive), else dist = +inf,
+ *                       idx = -1.  max_dist = +inf gives the exact unbounded answer.  Where a query qualifies, dist and idx
+ *                       are the bits ncw_nn_query writes when it resolves the query in its shells (the same d2 expression).
+ *                       A query with a NaN coordinate gets +inf / -1 without a walk; one with an infinite coordinate has
+ *                       d2 = +inf to every point: +inf / 0 when max_dist = +inf, else +inf / -1.
+ *                       The walk: fine shells 0..2 as ncw_nn_query, then Chebyshev shells of coarse blocks around the
+ *                       query's block.  A block or a cell is skipped when sum_a max(0, gap_a - margin)^2 > min(best d2, r2)
+ *                       (strict), gap_a = the distance along axis a from the query to the box of the block / cell; faces on
+ *                       the grid boundary give no gap, because points outside the grid box are clamped into the boundary
+ *                       cells.  An empty block costs one lookup.  The walk ends when (b - margin) > 0 and
+ *                       (b - margin)^2 > min(best d2, r2), b = distance to the faces of the visited blocks that are not on
+ *                       the grid boundary, or when the blocks cover the grid.  No atomics: dist / idx are a function of the
+ *                       inputs only, bitwise reproducible and the same for any split of the queries into launches.
+ *                       NCW_E_BADARG without a launch for a NULL pointer, a bad grid, B not a power of two in [1, 65536],
+ *                       margin < 0 or NaN, max_dist <= 0 or NaN; 0 without a launch for n <= 0.
  * ---------------------------------------------------------------------------------------- */
 typedef struct NcwNnGrid {
     float lo[3];
@@ -695,6 +716,10 @@ int ncw_nn_query(const float* pts_sorted, const int32_t* cell_range, const float
                  int32_t* n_escaped, void* stream);
 int ncw_nn_brute(const float* pts_sorted, int64_t m, const float* q, const int32_t* escaped, int64_t n_esc, uint64_t* scratch,
                  float* dist, int64_t* idx, void* stream);
+int ncw_nn_coarse(const int32_t* cell_range, const NcwNnGrid* grid, int B, int32_t* coarse, void* stream);
+int ncw_nn_query_within(const float* pts_sorted, const int32_t* cell_range, const int32_t* coarse, int B, const float* q,
+                        const int64_t* q_order, int64_t n, const NcwNnGrid* grid, float margin, float max_dist, float* dist,
+                        int64_t* idx, void* stream);
 
 
 /* ------------------------------------------------------------------------------------------

@@ -190,13 +190,24 @@ def far_reach(grid):
     return grid.max_shell * grid.h - 2.0 * grid.margin
 
 
-def correspondences(q32, inside, target, skip_beyond=None, stats=None):
+def gate_bound(gate):
+    """The radius `correspondences(bounded=True)` asks for at the float32 gate `gate`: gate (1 + 4 eps32), rounded to float32.
+    ncw_align_sums admits a pair when sqrtf(d2) <= gate, which implies d2 <= gate^2 (1 + eps)^2; the bound's float32 square is,
+    after its two roundings, still >= gate^2 (1 + 5 eps): every pair the sums admit is within the bound."""
+    return float(np.float32(float(gate) * (1.0 + 4.0 * evalmesh.F32_EPS)))
+
+
+def correspondences(q32, inside, target, skip_beyond=None, stats=None, bounded=False, gate=None):
     """(idx [N] int64, dist [N] float32): the nearest target point of every inside query (exact, ties to the smaller index);
     idx = -1 and dist = +inf for the others, which are not queried.
     skip_beyond (a gate, or None): the queries that `NNGrid` would hand to its brute-force pass over the whole cloud are left at
     idx = -1 / dist = +inf instead when the gate is below `far_reach(grid)`: they have no partner within the gate, so the pairs,
     the sums and the matrix are the same bits, and only the idx / dist reported for sources that take no part differ.  The
-    grid kernels are NNGrid.query's, called in its order; stats (dict) gets `escaped` and `skipped_far`."""
+    grid kernels are NNGrid.query's, called in its order; stats (dict) gets `escaped` and `skipped_far`.
+    bounded=True (with `gate`, the float32 gate of the iteration; skip_beyond is not read): the inside queries go to
+    `NNGrid.query_within` at `gate_bound(gate)` -- one launch, no escape list and no brute-force pass at ANY gate.  A query
+    with no target point within the bound is left at idx = -1 / dist = +inf; every pair within the gate has the idx and the
+    dist bits of the unbounded query.  stats gets `beyond` (those left at -1); `escaped` and `skipped_far` stay 0."""
     n = int(q32.shape[0])
     idx = torch.full((n,), -1, dtype=torch.int64, device=q32.device)
     dist = torch.full((n,), float("inf"), dtype=torch.float32, device=q32.device)
@@ -205,6 +216,12 @@ def correspondences(q32, inside, target, skip_beyond=None, stats=None):
         return idx, dist
     q = q32.index_select(0, sel).contiguous()
     g = target.grid
+    if bounded:
+        if gate is None:
+            raise ValueError("align.correspondences: bounded=True needs the gate")
+        d, i = g.query_within(q, gate_bound(gate), stats)
+        idx[sel], dist[sel] = i, d
+        return idx, dist
     if skip_beyond is None or not (float(skip_beyond) < far_reach(g)):
         d, i = g.query(q, stats)
         idx[sel], dist[sel] = i, d
@@ -249,7 +266,7 @@ def default_min_pairs(n):
 
 @torch.no_grad()
 def icp_similarity(src, target, init, gate0=None, shrink=0.85, gate_min=None, max_iter=60, with_scale=True, min_pairs=None,
-                   stats=None, skip_far=False):
+                   stats=None, skip_far=False, bounded=False):
     """Refines the 4x4 `init` so that it carries `src` [N,3] (a GPU tensor, or numpy moved to the target's device) onto `target`
     (AlignTarget).  Per iteration k with matrix T_k and gate g_k: transform, compact, NNGrid.query, sums over the pairs with
     dist <= g_k, T_{k+1} = the similarity of those pairs, g_{k+1} = max(g_k shrink, gate_min).  Stops when T_{k+1} equals T_k bit
@@ -258,6 +275,11 @@ def icp_similarity(src, target, init, gate0=None, shrink=0.85, gate_min=None, ma
     the target's box, gate_min = 4 x target.spacing().  The gates are rounded to float32 (what the kernels compare against).
     skip_far=True does not send a query that the grid cannot resolve to the brute-force pass once the gate is below
     `far_reach` (see `correspondences`): the same pairs, sums and matrices bit for bit, idx = -1 for those sources.
+    bounded=True asks `NNGrid.query_within` at a bound just above the gate (`gate_bound`) in EVERY iteration, also while the gate
+    is above `far_reach`, so no iteration runs the brute-force pass (skip_far is then not read).  The matrix, and every
+    iteration's pairs, rms and matrix, are the same bits as without it; in the history `escaped` and `skipped_far` read 0 and
+    `beyond` counts the inside sources left at idx = -1 (no target point within the bound); idx differs from the plain run
+    only on sources outside the mask, and only towards -1.
     Returns the 4x4 float64 matrix.  stats (dict) gets gate0 / gate_min / shrink / min_pairs, `iterations` (the solves made),
     `converged`, `history` (per iteration: gate, pairs, rms and max residual under T_k, mean pair distance, the matrix T_{k+1})
     and the last iteration's `idx` / `mask` (device tensors); with stats["keep_pairs"] set, every iteration's idx / mask as numpy
@@ -281,7 +303,7 @@ def icp_similarity(src, target, init, gate0=None, shrink=0.85, gate_min=None, ma
     for _ in range(int(max_iter)):
         q32, inside = transform_points(src, T, target, gate)
         qst = {}
-        idx, dist = correspondences(q32, inside, target, gate if skip_far else None, qst)
+        idx, dist = correspondences(q32, inside, target, gate if skip_far else None, qst, bounded=bounded, gate=gate)
         sums, counts = correspondence_sums(src, cp, target, idx, dist, gate, T)
         s, c = sums.cpu().numpy(), counts.cpu().numpy()  # the read-back: 22 numbers
         pairs = int(c[0])
@@ -293,7 +315,7 @@ def icp_similarity(src, target, init, gate0=None, shrink=0.85, gate_min=None, ma
         entry = {"gate": gate, "pairs": pairs, "rms": float(np.sqrt(s[17] / pairs)),
                  "max_residual": float(np.sqrt(np.array(c[1], dtype=np.int64).view(np.float64))),
                  "mean_distance": float(s[18] / pairs), "matrix": T_new.tolist(), "escaped": qst.get("escaped", 0),
-                 "skipped_far": qst.get("skipped_far", 0)}
+                 "skipped_far": qst.get("skipped_far", 0), "beyond": qst.get("beyond", 0)}
         if keep:
             entry["idx"], entry["mask"] = idx.cpu().numpy(), mask.cpu().numpy()
         history.append(entry)
@@ -352,7 +374,10 @@ def estimate_sfm2gt(data_dir, gt_pcd_path, sfm_path="dense/sparse", init="config
     (ply.read_points) by `icp_similarity` from `initial_matrix(data_dir, init, pairs)`; **icp are icp_similarity's options.
     Returns (4x4 float64, report).  report: initial_matrix, matrix, correction (matrix inv(initial): scale, rotation_deg,
     translation), iterations, converged, source_points, pairs, inlier_share, rms, max_residual, gate0 / gate_min / shrink /
-    min_pairs / with_scale, matched_bbx (the GT-frame box of the matched GT points: a suggestion for eval_bbx), history."""
+    min_pairs / with_scale, matched_bbx (the GT-frame box of the matched GT points: a suggestion for eval_bbx), history.
+    `bounded` defaults to True here (icp_similarity's own default stays False): the matrix, sfm2gt.yaml and every iteration's
+    pairs, rms and matrix are the same bits as with bounded=False; in the report's history `escaped` and `skipped_far` read 0
+    and `beyond` counts the sources left at idx = -1."""
     src = evalmesh.read_points3d_filtered(os.path.join(data_dir, sfm_path), track_length, reproj_error)
     if src.shape[0] < 3:
         raise ValueError("%d SfM points pass track_length > %s and reproj_error < %s" % (src.shape[0], track_length, reproj_error))
@@ -361,6 +386,9 @@ def estimate_sfm2gt(data_dir, gt_pcd_path, sfm_path="dense/sparse", init="config
     target = AlignTarget(gt, device, gate_max=icp.get("gate0"))
     st = {}
     icp.setdefault("skip_far", True)  # the matrix and the report are the same bits either way; only unpaired sources' idx differ
+    # the radius-bounded query: the same matrix and the same pairs, rms and matrix in every iteration, and no brute-force pass at
+    # the early gates (profiles/align/README.md: faster at every gate measured); the history then reports `beyond`
+    icp.setdefault("bounded", True)
     T = icp_similarity(src, target, T0, stats=st, **icp)
     last = st["history"][-1]
     matched = target.points[st["idx"][st["mask"]]]

@@ -41,6 +41,7 @@ from .ply import read_points as read_ply_points  # noqa: F401  (a binding only: 
 F32_EPS = float(np.finfo(np.float32).eps)
 MAX_CELLS = 1 << 24  # cap of the dense cell table (two int32 per cell)
 MAX_SHELL = 8        # Chebyshev shells a query walks before it is handed to the brute-force kernel
+COARSE_MAX_BLOCKS = 1 << 16  # cap of the coarse occupancy table of NNGrid.query_within (one int32 per block of cells)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -74,7 +75,8 @@ class NNGrid:
     are clamped into the boundary cells.  That keeps the search exact: a point in a cell below the block's lower face lies
     below that face whether it was clamped or not, and the faces on the grid boundary never enter the stop bound.
     `coord_max`: the largest |coordinate| of P and the queries (sets the rounding margin of the stop test).  Built once,
-    queried with `query`."""
+    queried with `query` (every query answered; the far ones by a brute-force pass) or `query_within` (the nearest point within a
+    radius, or nothing: one launch over a second, coarse occupancy level, no brute-force pass)."""
 
     def __init__(self, ref32, coord_max, max_shell=MAX_SHELL, target_cells=None):
         if not ref32.is_cuda:
@@ -111,6 +113,7 @@ class NNGrid:
         h, dims = _grid_for(self.ext, target_cells)
         self.h, self.dims = h, dims
         self.ncells = int(dims[0] * dims[1] * dims[2])
+        self.coarse = None  # the coarse level of query_within: built on its first call
         g = L.NcwNnGrid()
         for a in range(3):
             g.lo[a], g.dim[a] = self.lo[a], dims[a]
@@ -153,6 +156,55 @@ class NNGrid:
             stats["escaped"] = stats.get("escaped", 0) + ne
         return dist, idx
 
+    def build_coarse(self, block=None):
+        """The coarse occupancy level of `query_within`: the number of points per block of `block`^3 fine cells (int32,
+        ceil(dim / block) entries per axis), built by `ncw_nn_coarse` and kept with the grid.  The rule for `block` when none
+        is given: the smallest power of two >= 4 whose table has at most COARSE_MAX_BLOCKS entries -- small enough that an empty
+        region costs few lookups, and a table (256 KiB at the most) that stays in the caches."""
+        if block is None:
+            block = 4
+            while np.prod([-(-d // block) for d in self.dims], dtype=np.float64) > COARSE_MAX_BLOCKS:
+                block *= 2
+        block = int(block)
+        if block < 1 or block > 65536 or block & (block - 1):
+            raise ValueError("evalmesh.NNGrid.build_coarse: block must be a power of two in [1, 65536], got %r" % (block,))
+        cdims = [-(-d // block) for d in self.dims]
+        coarse = torch.empty(cdims[0] * cdims[1] * cdims[2], dtype=torch.int32, device=self.dev)
+        L.check(L.get_lib().ncw_nn_coarse(L.ptr(self.range), C.byref(self.cgrid), block, L.ptr(coarse), L.stream_ptr(self.dev)),
+                "ncw_nn_coarse")
+        self.coarse, self.coarse_block, self.coarse_dims = coarse, block, cdims
+        return coarse
+
+    def query_within(self, q32, max_dist, stats=None):
+        """(dist [N] f32, idx [N] int64): every query's nearest point of P if it lies within `max_dist` (d^2 <= float32(max_dist)^2,
+        inclusive), else dist = +inf and idx = -1.  Exact, ties to the smaller index; where a query qualifies, the bits are
+        those of `query`'s shell walk.  One launch answers every query (`ncw_nn_query_within`): no escape list, no brute-force
+        pass; max_dist = inf gives the unbounded answer.  The coarse level is built on the first call (`build_coarse`).
+        stats (dict) gets `beyond` (the queries answered -1).  ValueError unless max_dist > 0."""
+        max_dist = float(max_dist)
+        if not max_dist > 0:
+            raise ValueError("evalmesh.NNGrid.query_within: max_dist must be > 0, got %r" % (max_dist,))
+        if not q32.is_cuda:
+            raise L.NeuconwHipError("evalmesh.NNGrid.query_within: the queries are not on a GPU; there is no CPU fallback")
+        lib = L.get_lib()
+        if self.coarse is None:
+            self.build_coarse()
+        n = int(q32.shape[0])
+        q32 = q32.contiguous()
+        dist = torch.empty(n, dtype=torch.float32, device=self.dev)
+        idx = torch.empty(n, dtype=torch.int64, device=self.dev)
+        if n:
+            keys = torch.empty(n, dtype=torch.int32, device=self.dev)
+            s = L.stream_ptr(self.dev)
+            L.check(lib.ncw_nn_cell_keys(L.ptr(q32), n, C.byref(self.cgrid), L.ptr(keys), s), "ncw_nn_cell_keys")
+            q_order = torch.sort(keys, stable=True)[1].contiguous()
+            L.check(lib.ncw_nn_query_within(L.ptr(self.pts), L.ptr(self.range), L.ptr(self.coarse), self.coarse_block, L.ptr(q32),
+                                            L.ptr(q_order), n, C.byref(self.cgrid), float(self.margin), max_dist, L.ptr(dist),
+                                            L.ptr(idx), s), "ncw_nn_query_within")
+        if stats is not None:
+            stats["beyond"] = stats.get("beyond", 0) + (int((idx < 0).sum()) if n else 0)
+        return dist, idx
+
 
 def recentre(ref, query):
     """Both clouds moved to their common box centre in float64, then cast to f32 (scene coordinates are metres and may be
@@ -169,11 +221,16 @@ def recentre(ref, query):
 
 
 @torch.no_grad()
-def nn_distances(ref, query, max_shell=MAX_SHELL, stats=None):
+def nn_distances(ref, query, max_shell=MAX_SHELL, stats=None, max_dist=None):
     """For every query point its Euclidean distance to the nearest point of `ref` and that point's index -- exact, ties to the
     smaller index (utils/eval_utils.py:126-154 `nn_correspondance(ref, query)`).  ref [M,3], query [N,3]: GPU tensors (any
     float dtype).  Returns (dist [N] float32, idx [N] int64); empty results when either side is empty (as the reference).
-    stats (dict, optional) gets the grid shape and the number of queries that took the brute-force path (`escaped`)."""
+    stats (dict, optional) gets the grid shape and the number of queries that took the brute-force path (`escaped`).
+    max_dist (a number > 0, default None = no bound, the path above unchanged): only a nearest point within max_dist is
+    reported, dist = +inf and idx = -1 otherwise (`NNGrid.query_within`: one launch, no brute-force pass; stats gets `beyond`
+    instead of `escaped`).  ValueError unless max_dist > 0."""
+    if max_dist is not None and not float(max_dist) > 0:
+        raise ValueError("evalmesh.nn_distances: max_dist must be > 0, got %r" % (max_dist,))
     if not (ref.is_cuda and query.is_cuda):
         raise L.NeuconwHipError("evalmesh.nn_distances: the clouds are not on a GPU; there is no CPU fallback")
     dev = ref.device
@@ -184,6 +241,8 @@ def nn_distances(ref, query, max_shell=MAX_SHELL, stats=None):
     grid = NNGrid(r32, cmax, max_shell=max_shell)
     if stats is not None:
         stats.update(dims=list(grid.dims), cells=grid.ncells, refined=grid.refined)
+    if max_dist is not None:
+        return grid.query_within(q32, max_dist, stats)
     return grid.query(q32, stats)
 
 

@@ -213,14 +213,18 @@ def backproject_matrix(K, pose, centre=None):
 # ---------------------------------------------------------------------------------------------------
 class Target:
     """The cloud to filter (utils/reproj_filter.py:177-189): every vertex of target_file (no welding) in GT coordinates,
-    its colours (zeros without), and one NNGrid over it (recentred on its box centre in float64, as nn_distances does)."""
+    its colours (zeros without), and one NNGrid over it (recentred on its box centre in float64, as nn_distances does).
+    bounded (default True): `mark` asks for the nearest vertex WITHIN the threshold only (NNGrid.query_within: one launch, no
+    brute-force pass for back-projected points that have no vertex nearby); the flags are the same either way, bounded=False is
+    the earlier path, kept for the comparison."""
 
-    def __init__(self, xyz, rgb, thr, device):
+    def __init__(self, xyz, rgb, thr, device, bounded=True):
         self.xyz = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
         self.rgb = np.zeros(self.xyz.shape, dtype=np.uint8) if rgb is None else np.asarray(rgb, dtype=np.uint8).reshape(-1, 3)
         self.m = self.xyz.shape[0]
         self.dev = device
         self.thr = float(thr)
+        self.bounded = bool(bounded)
         self.flags = torch.zeros(max(1, self.m), dtype=torch.uint8, device=device)
         self.centre = (self.xyz.min(0) + self.xyz.max(0)) / 2 if self.m else np.zeros(3)
         self.grid = None
@@ -236,7 +240,12 @@ class Target:
         n = int(pts32.shape[0])
         if n == 0 or self.grid is None:
             return
-        dist, idx = self.grid.query(pts32)
+        if self.bounded:
+            # ncw_raster_mark marks where sqrtf(d2) < thr (float32), which implies d2 < thr^2 (1 + eps)^2; the float32 square of
+            # thr (1 + 4 eps) is, after its two roundings, still >= thr^2 (1 + 5 eps): every vertex it marks is within the bound
+            dist, idx = self.grid.query_within(pts32, float(np.float32(self.thr)) * (1.0 + 4.0 * evalmesh.F32_EPS))
+        else:
+            dist, idx = self.grid.query(pts32)
         L.check(L.get_lib().ncw_raster_mark(L.ptr(dist), L.ptr(idx), n, self.thr, self.m, L.ptr(self.flags),
                                             L.stream_ptr(self.dev)), "ncw_raster_mark")
 
@@ -372,7 +381,7 @@ def render_cloud_depth(points, scene_config, voxel_size, K, pose, height, width,
 
 @torch.no_grad()
 def reproj_filter(src_file, target_file, data_path, output_path, gt=False, voxel_size=0.01, visualize=False, znear=ZNEAR,
-                  zfar=ZFAR, cull="back", device=None, verbose=True, keep_faces=False, min_corners=1, min_component_faces=0):
+                  zfar=ZFAR, cull="back", device=None, verbose=True, keep_faces=False, min_corners=1, min_component_faces=0, bounded=True):
     """utils/reproj_filter.py: keep the vertices of target_file that a training view of data_path sees on src_file.
     A source WITH faces (a mesh).  Per view: render the depth of the source mesh, back-project every pixel with depth > 0
     at its integer pixel coordinates, mark the nearest target vertex when it is closer than 2 sqrt(2) voxel_size (GT units).
@@ -399,6 +408,8 @@ def reproj_filter(src_file, target_file, data_path, output_path, gt=False, voxel
     recall then counts against the model.  The one-ring rule admits at most one triangle's width of surface beyond the marked
     vertices.  min_corners = 3 is for whoever wants "nothing the reference would drop": its vertex set is a subset of the
     rows of reprojected.ply.
+    `bounded` (mesh source only; default True): the marking asks for the nearest target vertex within the threshold only
+    (`Target`): reprojected.ply and reprojected_mesh.ply are byte for byte what bounded=False, the earlier path, writes.
     Returns (xyz float64 [K,3], rgb uint8 [K,3]) -- the rows of reprojected.ply, whatever keep_faces is."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     log = print if verbose else (lambda *a, **k: None)
@@ -431,7 +442,7 @@ def reproj_filter(src_file, target_file, data_path, output_path, gt=False, voxel
         if keep_faces:
             _write_filtered_mesh(output_path, t_xyz, t_faces, t_rgb, flags, min_corners, min_component_faces, dev, log)
         return xyz, rgb
-    target = Target(t_xyz, t_rgb, 2 * np.sqrt(2) * voxel_size, dev)
+    target = Target(t_xyz, t_rgb, 2 * np.sqrt(2) * voxel_size, dev, bounded=bounded)
     mesh = RasterMesh(s_verts, s_faces, dev)
     zbuf = None
     for v in views:

@@ -10,7 +10,11 @@ All in one call, warm, device events, medians over --repeat:
     host solve with its read-back of 22 numbers -- at the first gate and at a late one;
   * the sums launch beside the same 20 sums composed in torch (index_select, a mask, einsum / sum in float64), alternating, with
     the distance between the two results and whether two runs of each agree bit for bit;
-  * a whole icp_similarity call from a perturbed start, its iterations and the error of the matrix it returns.
+  * a whole icp_similarity call from a perturbed start, its iterations and the error of the matrix it returns;
+  * the radius-bounded query (NNGrid.query_within: ncw_nn_query_within at align.gate_bound(gate), one launch, no brute-force pass)
+    beside the query stage at both gates, alternating in the same loop (`query_within`, with the min / max of both), and a third
+    whole call with bounded=True beside the plain and the skip_far ones; --icp_repeat further skip_far / bounded pairs,
+    alternating, give the spread of the whole call (`icp_call.bounded`).
 The cloud: three rectangles meeting at a corner and a Gaussian bump, 30 x 20 x 15 units, uniform by area, offset far from the
 origin.  The source: target points carried back by a known similarity, a fifth of them replaced by uniform outliers.
 Prints one JSON line and writes it to --out."""
@@ -118,6 +122,20 @@ def iteration_stages(src, cp, target, T, gate, repeat):
             return idx, dist, ne
 
         r["query"], (idx, dist, ne) = timed(query)
+
+        def query_within():
+            d = torch.empty(n, dtype=torch.float32, device=dev)
+            i = torch.empty(n, dtype=torch.int64, device=dev)
+            L.check(lib.ncw_nn_query_within(L.ptr(g.pts), L.ptr(g.range), L.ptr(g.coarse), g.coarse_block, L.ptr(q), L.ptr(order), n,
+                                            C.byref(g.cgrid), float(g.margin), align.gate_bound(gate), L.ptr(d), L.ptr(i), s), "within")
+            idx = torch.full((src.shape[0],), -1, dtype=torch.int64, device=dev)
+            dist = torch.full((src.shape[0],), float("inf"), dtype=torch.float32, device=dev)
+            idx[sel], dist[sel] = i, d
+            return idx, dist
+
+        if g.coarse is None:
+            g.build_coarse()
+        r["query_within"], (idx_w, dist_w) = timed(query_within)
         r["sums"], (sums, counts) = timed(lambda: align.correspondence_sums(src, cp, target, idx, dist, gate, T))
 
         def solve():
@@ -125,11 +143,17 @@ def iteration_stages(src, cp, target, T, gate, repeat):
             return align.similarity_from_sums(int(ch[0]), sh, cp, target.centre), int(ch[0])
 
         r["solve_with_readback"], (_, pairs) = timed(solve)
-        r["total"] = sum(r.values())
+        r["total"] = sum(v for k, v in r.items() if k != "query_within")
         if it:
             rows.append(r)
     out = {k: float(np.median([r[k] for r in rows])) for k in rows[0]}
-    out.update(inside=n, pairs=pairs, escaped=ne, gate=float(gate))
+    m, mw = (idx >= 0) & (dist <= gate), (idx_w >= 0) & (dist_w <= gate)
+    out.update(inside=n, pairs=pairs, escaped=ne, gate=float(gate), query_min_max=[min(r["query"] for r in rows), max(r["query"] for r in rows)],
+               query_within_min_max=[min(r["query_within"] for r in rows), max(r["query_within"] for r in rows)],
+               within_bound=align.gate_bound(gate), within_beyond=int((idx_w[sel] < 0).sum()),
+               within_same_pairs=bool(torch.equal(m, mw) and torch.equal(idx[m], idx_w[m]) and torch.equal(dist[m], dist_w[m])),
+               coarse_block=g.coarse_block, coarse_entries=int(g.coarse.numel()))
+    out["query_within_outside_query_spread"] = bool(out["query_within_min_max"][1] < out["query_min_max"][0])
     return out, idx, dist
 
 
@@ -141,7 +165,9 @@ def main(argv=None):
     ap.add_argument("--repeat", type=int, default=7)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--max_shell", type=int, default=None, help="NNGrid shells before the brute-force path (default: evalmesh.MAX_SHELL)")
-    ap.add_argument("--no_icp", action="store_true", help="skip the two whole icp_similarity calls")
+    ap.add_argument("--no_icp", action="store_true", help="skip the whole icp_similarity calls")
+    ap.add_argument("--no_plain_icp", action="store_true", help="skip the plain whole call (brute-force pass in every iteration): skip_far and bounded only")
+    ap.add_argument("--icp_repeat", type=int, default=3, help="further skip_far / bounded whole calls, alternating: the spread")
     ap.add_argument("--out", default=os.path.join("profiles", "align", "align_bench.json"))
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
@@ -223,9 +249,28 @@ def main(argv=None):
     if args.no_icp:
         return finish(res, args)
     # a whole call, as icp_similarity runs it and with skip_far (the same matrices, bit for bit)
-    st, st2 = {}, {}
-    t_icp, T = timed(lambda: align.icp_similarity(src, target, init, stats=st))
+    st, st2, st3 = {}, {}, {}
     t_icp2, T2 = timed(lambda: align.icp_similarity(src, target, init, stats=st2, skip_far=True))
+    t_icp3, T3 = timed(lambda: align.icp_similarity(src, target, init, stats=st3, bounded=True))
+    same3 = all(np.array_equal(a["matrix"], b["matrix"]) and a["pairs"] == b["pairs"] and a["rms"] == b["rms"]
+                for a, b in zip(st2["history"], st3["history"]))
+    t_skip, t_bnd = [t_icp2], [t_icp3]
+    for _ in range(args.icp_repeat):
+        t_skip.append(timed(lambda: align.icp_similarity(src, target, init, skip_far=True))[0])
+        t_bnd.append(timed(lambda: align.icp_similarity(src, target, init, bounded=True))[0])
+    bounded = {"ms": float(np.median(t_bnd)), "min_max_ms": [min(t_bnd), max(t_bnd)], "skip_far_ms": float(np.median(t_skip)),
+               "skip_far_min_max_ms": [min(t_skip), max(t_skip)], "calls_each": len(t_bnd), "iterations": st3["iterations"],
+               "same_bits_every_iteration": bool(same3 and np.array_equal(T2, T3) and st2["iterations"] == st3["iterations"]),
+               "outside_skip_far_spread": bool(max(t_bnd) < min(t_skip)),
+               "beyond_per_iteration": [h["beyond"] for h in st3["history"]],
+               "escaped_per_iteration": [h["escaped"] for h in st3["history"]]}
+    if args.no_plain_icp:
+        res["icp_call"] = {"bounded": bounded, "ms_skip_far": t_icp2, "iterations_skip_far": st2["iterations"],
+                           "far_reach": align.far_reach(target.grid), "gate_per_iteration": [h["gate"] for h in st2["history"]],
+                           "skipped_far_per_iteration": [h["skipped_far"] for h in st2["history"]],
+                           "max_abs_error_over_max_abs_truth": float(np.abs(T3 - truth).max() / np.abs(truth).max())}
+        return finish(res, args)
+    t_icp, T = timed(lambda: align.icp_similarity(src, target, init, stats=st))
     same = all(np.array_equal(a["matrix"], b["matrix"]) and a["pairs"] == b["pairs"] for a, b in zip(st["history"], st2["history"]))
     res["icp_call"] = {"ms": t_icp, "ms_skip_far": t_icp2, "iterations": st["iterations"], "iterations_skip_far": st2["iterations"],
                        "converged": st["converged"], "ms_per_iteration": t_icp / st["iterations"],
@@ -237,6 +282,8 @@ def main(argv=None):
                        "gate_per_iteration": [h["gate"] for h in st2["history"]],
                        "skipped_far_per_iteration": [h["skipped_far"] for h in st2["history"]],
                        "escaped_per_iteration": [h["escaped"] for h in st["history"]]}
+    bounded["same_bits_every_iteration"] = bool(bounded["same_bits_every_iteration"] and same and np.array_equal(T, T3))
+    res["icp_call"]["bounded"] = bounded
     return finish(res, args)
 
 

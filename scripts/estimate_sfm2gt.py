@@ -10,6 +10,8 @@ from the identity, --init <file> from a matrix file (16 or 12 numbers as text, .
 collinear) is solved in closed form and used instead.  The source is the COLMAP points of <data_dir>/<reconstuct_path> with MORE
 THAN --track_length observations and a mean reprojection error BELOW --reproj_error.  --gate0 / --gate_min default to 0.2 x the
 longest edge of the cloud's box and 4 x its median point spacing; both are recorded in the report.
+The nearest-neighbour queries are radius-bounded by default (nearest target point within the gate, or none: one launch, no
+brute-force pass); --no_bounded takes the earlier path -- the same sfm2gt.yaml byte for byte, slower.
 Writes report.json (initial and final matrix, the correction's scale / rotation / translation, iterations, pairs and inlier share,
 rms, the ground-truth box of the matched points as a suggestion for eval_bbx, the per-iteration history) and sfm2gt.yaml into
 --out_dir and prints the matrix.  <data_dir>/config.yaml is left alone unless --write_config is given: then its sfm2gt value is
@@ -40,6 +42,8 @@ def build_parser():
     ap.add_argument("--gate_min", type=float, default=None, help="smallest gate (default 4 x the cloud's median point spacing)")
     ap.add_argument("--max_iter", type=int, default=60)
     ap.add_argument("--min_pairs", type=int, default=None, help="fail below this many pairs (default 10 %% of the source)")
+    ap.add_argument("--no_bounded", action="store_true", help="answer the nearest-neighbour queries without the radius bound (the earlier "
+                    "path, brute-force pass included): the same sfm2gt.yaml, slower; kept for the comparison")
     ap.add_argument("--out_dir", type=str, default=os.path.join("samples", "align"))
     ap.add_argument("--write_config", action="store_true", help="replace sfm2gt in <data_dir>/config.yaml (backup: config.yaml.bak)")
     ap.add_argument("--device", type=str, default="cuda:0")
@@ -79,7 +83,8 @@ def main(argv=None):
         raise FileExistsError("%s exists: refusing before the run" % os.path.join(args.data_dir, "config.yaml.bak"))
     T, rep = align.estimate_sfm2gt(args.data_dir, args.gt_pcd_path, args.reconstuct_path, args.init, pairs, args.track_length,
                                    args.reproj_error, args.device, gate0=args.gate0, shrink=args.shrink, gate_min=args.gate_min,
-                                   max_iter=args.max_iter, with_scale=not args.no_scale, min_pairs=args.min_pairs)
+                                   max_iter=args.max_iter, with_scale=not args.no_scale, min_pairs=args.min_pairs,
+                                   bounded=not args.no_bounded)
     os.makedirs(args.out_dir, exist_ok=True)
     with open(os.path.join(args.out_dir, "report.json"), "w") as fh:
         json.dump(rep, fh, indent=1)
