@@ -238,7 +238,10 @@ typedef struct NcwColorNet {
     const void* w_f_lo; const void* w_e_lo[4]; const void* w_l_lo[8];
     /* with the residual matrices present: 1 = the ACTIVATIONS of every layer as fp16 hi + lo pairs too (a third pass W_hi x_lo; rbf
      * 8 / 16 only).  Default at d_feature = 512, the shipped width: with 8 + 16 samples one sample carries a ray and the
-     * activations' rounding was, with the normals', what kept rays above 1e-4 on trained weights (ncw_color.hip).  Forward only. */
+     * activations' rounding was, with the normals', what kept rays above 1e-4 on trained weights (ncw_color.hip).  Forward only.
+     * At rbf / rbh / rbc = 8 / 4 / 8 the value 1 runs the weights-stationary kernel (csrc/ncw_split.hip color_fwdS_kernel: eight waves per
+     * workgroup, the same bits); 2 = the pairs through the generic register-resident kernel, as at every other width (bisecting,
+     * tests/test_gpu_color_fwd_ws.py). */
     int32_t act_split;
     int32_t _pad;
 } NcwColorNet;

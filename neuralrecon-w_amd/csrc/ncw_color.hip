@@ -7,20 +7,6 @@
 
 namespace NCW_NS {
 
-// AUX2 (1 block): [points (3) | normals (3) | 0...]   (neuconw.py:147-148)
-NCW_DEV void build_aux2(CVec<1>& aux, const float (&x)[3], const float (&nrm)[3], int lane) {
-    const int h = lane >> 5;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        float v = 0.f;
-        if (ncw_feat_of(r, 0) < 6) {
-            const int f = ncw_feat_of(r, 0) + 4 * h;
-            v = f == 0 ? x[0] : f == 1 ? x[1] : f == 2 ? x[2] : f == 3 ? nrm[0] : f == 4 ? nrm[1] : f == 5 ? nrm[2] : 0.f;
-        }
-        aux.v[0][r] = v;
-    }
-}
-
 // acc += W in with W as a 16-bit hi + lo pair (w_lo: the residual matrix h16(W - h16(W)), same packed shape; nullptr = hi only):
 // two passes of the weight ring over the same activations.  self_bytes = first-chunk bytes of this matrix shape (what the
 // call before must have prefetched: the lo pass re-uses it), w_next / next_bytes as mma_stream.
@@ -400,6 +386,11 @@ static bool color_ok(const NcwColorNet* net) {
         }                                                                                                        \
     } while (0)
 
+#ifdef NCW_HALF_F16
+// csrc/ncw_split.hip: the weights-stationary forward of key 80408 with weights and activations as pairs
+int ncw_color_fwdS_launch_f16(const NcwColorNet* net, const NcwPoints& src, int64_t n, const float* normals, const float* a,
+                              const void* feat_stash, float* rgb, const NcwColorStash& stash, hipStream_t st);
+#endif
 #ifndef NCW_HALF_F16
 extern "C" int ncw_color_fwd_f16(const NcwColorNet*, int, const NcwPoints*, int64_t, const float*, const float*, const void*, float*,
                                  const NcwColorStash*, void*);
@@ -430,6 +421,10 @@ extern "C" int NCW_FN(ncw_color_fwd)(const NcwColorNet* net, int prec, const Ncw
             else return NCW_E_UNSUPPORTED;                                                                                                      \
         } while (0)
         if (net->act_split) {  // the activations as hi + lo pairs too (the two widths that ship: d_feature 256 / 512)
+#ifdef NCW_HALF_F16
+            // d_feature 256: the weights-stationary kernel (eight waves; the same bits); act_split == 2 keeps the generic instance
+            if (key == 80408 && net->act_split != 2) return ncw_color_fwdS_launch_f16(net, *pts, n, normals, a, feat_stash, rgb, *stash, st);
+#endif
 #define NCW_COLOR_ASPLIT_DISPATCH(KERNEL)                                                                                                  \
         do {                                                                                                                                    \
             if (key == 80408) NCW_LAUNCH_TILES((KERNEL<PrecBF16, 8, 4, 8, 2>), n, st, *net, *pts, n, normals, a, feat_stash, rgb, *stash);        \

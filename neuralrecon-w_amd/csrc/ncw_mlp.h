@@ -319,6 +319,20 @@ NCW_DEV void build_aux1(CVec<3>& aux, const float (&dir)[3], const float* __rest
         }
 }
 
+// AUX2 (1 block): [points (3) | normals (3) | 0...]   (neuconw.py:147-148)
+NCW_DEV void build_aux2(CVec<1>& aux, const float (&x)[3], const float (&nrm)[3], int lane) {
+    const int h = lane >> 5;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        float v = 0.f;
+        if (ncw_feat_of(r, 0) < 6) {
+            const int f = ncw_feat_of(r, 0) + 4 * h;
+            v = f == 0 ? x[0] : f == 1 ? x[1] : f == 2 ? x[2] : f == 3 ? nrm[0] : f == 4 ? nrm[1] : f == 5 ? nrm[2] : 0.f;
+        }
+        aux.v[0][r] = v;
+    }
+}
+
 // 16-bit modes: the AUX1 columns of an appearance head's first layer are evaluated once per RAY in fp32 (ncw_aux_ray_bias) and
 // enter the fused kernels as a per-ray bias row [32 RB] (f32, C-layout feature order = plain feature index); the AUX1
 // operand of the forward pass is then zero.

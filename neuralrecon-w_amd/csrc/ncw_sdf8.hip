@@ -1,7 +1,9 @@
 // Weights-stationary fused MLP kernels, W = 256, 16-bit: sdf_fwdB, nerf_fwdB, nerf_bwdB.
 // (The 8-wave / half-layer pilot of round 1 and the sdf_bwd / color_fwd ports that did not beat the
 // two-workgroups-per-CU kernels were removed in round 2, the burst inference kernel sdf_inferB -- superseded by
-// ncw_pp.hip's fine-interleaved sdf_inferC -- in round 3; numbers in DESIGN.md.)
+// ncw_pp.hip's fine-interleaved sdf_inferC -- in round 3; numbers in DESIGN.md.  Round 9 built the colour forward in this
+// structure again, as color_fwdS_kernel of ncw_split.hip: since round 6 the fp16 forward it replaces carries weights and
+// activations as hi + lo pairs and owns the CU at ONE wave per SIMD, no longer two workgroups per CU; NOTEBOOK R9.1.)
 #include "ncw_mlp.h"
 
 namespace {

@@ -1,4 +1,5 @@
-// Split-precision SDF VALUE path, W = 256, fp16 build only: sdf_inferS, sdf_fwdS.
+// Split-precision SDF VALUE path, W = 256, fp16 build only: sdf_inferS, sdf_fwdS; in the same structure the background
+// NeRF's forward refinement (nerf_refineS) and the colour network's forward (color_fwdS), further down.
 //
 // NeuS turns the SDF into opacity through sigmoid(sdf * inv_s), inv_s = exp(10 * variance) (models/neuconw.py:173-179,
 // rendering/renderer.py:624-632; the sampler uses fixed 512 / 1024, renderer.py:527-533).  inv_s is 20 at initialisation and
@@ -1089,6 +1090,335 @@ __global__ __launch_bounds__(64 * NS_WAVES) void nerf_refineS_kernel(NcwNerfNet 
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Colour network FORWARD in the weights-stationary split structure (round 9): color_fwd_kernel<PrecBF16, 8, 4, 8, 2> of
+// ncw_color.hip (d_feature 256, head 128, trunk 256; weights AND activations as fp16 hi + lo pairs) with EIGHT waves per
+// workgroup -- two per SIMD, where the register-resident form owns the CU at one -- and the same bits: per accumulator the
+// bias (+ the per-ray fp32 head row at e[0]), then W_hi x_hi, W_hi x_lo for the k-units in order, then W_lo x_hi for the
+// k-units in order (mma_stream_split3: two passes of the weight ring).  That order decides the weight schedule: a layer's
+// slice is two register sets of 16 units, HI and LO; pass 1 uses HI on both activation planes while LO lands, pass 2 uses LO
+// while the NEXT layer's HI lands in the registers pass 1 has left.
+// Work: 4 tiles (128 points) per workgroup, the launch grid of the generic kernel.  Wave w owns output block w of a 256-wide
+// layer (w_f, w_l[l]) for the four tiles, block w & 3 of tile pair w >> 2 in the 128-wide head (w_e[i]), and wave t the rgb
+// row of tile t.  LDS: activations [tile][16 units][hi | lo] (128 KiB, rewritten in place behind a barrier), AUX1
+// [tile][6 units] hi only (24 KiB), AUX2 [tile][hi | lo] (8 KiB: unit 0 of the block; unit 1 is beyond lin0's K_REAL).
+// With the per-ray head rows (NcwColorStash.aux_bias, the default) the generic kernel multiplies a ZERO AUX1 operand: those
+// units are left out here (+0 products; the sign of a zero sum dies in the ReLU behind it).
+// TRAIN = false: the forward-only render, the same rgb bit for bit, nothing stashed.
+// ------------------------------------------------------------------------------------------------
+constexpr int CW_X1 = SS_TILES * 6 * 1024;  // AUX1: [tile][6 units][64 lanes x 16 B]
+constexpr int CW_X2 = SS_TILES * 2 * 1024;  // AUX2: [tile][hi | lo][64 lanes x 16 B]
+constexpr int CW_TILE = 16 * 2 * 64;        // fragments per tile of the activation buffer
+
+// units 0 .. NU of output block ob of a packed matrix (unit = `stride` blocks) through ONE running uniform pointer, pinned in
+// scalar registers per unit (sa_mma: left as (u * stride + ob) with a run-time stride hipcc forms 64-bit vector addresses)
+template <int NU>
+NCW_DEV void cw_load(bf16x8 (&w)[16], const void* m, int stride, int ob, int lane) {
+    const char* p = (const char*)m + (size_t)ob * 1024;
+    const size_t step = (size_t)stride * 1024;
+#pragma unroll
+    for (int q = 0; q < NU; ++q) {
+        asm volatile("" : "+s"(p));
+        w[q] = ss_gload(p, 0, lane);
+        p += step;
+    }
+    __builtin_amdgcn_sched_barrier(0);  // the requests stay here: ahead of the pass that hides them (gamma_job above)
+}
+
+// acc[t] += w[q] . in[t][q], q < NU, for NT tiles in pairs (consecutive MFMAs alternate between two accumulators); NB = 2:
+// the hi and then the lo fragment of every unit (W_hi x_hi, W_hi x_lo), 1: the hi fragment only.  in = first tile, first
+// unit, + lane; tiles TS and units US fragments apart, lo = hi + 64.  The B fragments of a step (one unit of one tile pair)
+// come through a register ring CW_RD steps ahead of their MFMAs, the issue order pinned per step (ss_mma).
+// Depth: a pair step is 16 registers, and a 256-wide layer holds 192 beside the ring (4 accumulators, the HI and the LO set): two
+// steps ahead (three slots, 48 registers) is the deepest that fits, at 248 VGPRs, as in ss_mma
+template <int NT, int NU, int NB, int TS, int US>
+NCW_DEV void cw_mma(f32x16 (&acc)[NT], const bf16x8 (&w)[16], const ss_lfrag* in) {
+    constexpr int CW_RD = 2;
+    constexpr int NS = (NT / 2) * NU, RD = CW_RD < NS ? CW_RD : NS, R = RD + 1 < NS ? RD + 1 : NS;
+    bf16x8 b[R][2 * NB];
+    // the second tile pair through a base of its own: the activation buffer is 128 KiB and a ds_read offset 16 bits -- left to
+    // hipcc, every fragment beyond 64 KiB gets an address register, hoisted out of the layer loop (the loop then spills its slice)
+    const ss_lfrag* in2 = in + 2 * TS;
+    asm volatile("" : "+v"(in2));
+    auto ring_read = [&](int s) {
+        const ss_lfrag* p0 = (s / NU ? in2 : in) + (s % NU) * US;
+        const ss_lfrag* p1 = p0 + TS;
+        b[s % R][0] = p0[0];
+        b[s % R][1] = p1[0];
+        if (NB == 2) { b[s % R][2] = p0[64]; b[s % R][3] = p1[64]; }
+    };
+#pragma unroll
+    for (int s = 0; s < RD; ++s) ring_read(s);
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        if (s + RD < NS) ring_read(s + RD);
+        const int tp = 2 * (s / NU), q = s % NU;
+        const bf16x8 (&f)[2 * NB] = b[s % R];
+        acc[tp] = NCW_MFMA_H(w[q], f[0], acc[tp], 0, 0, 0);
+        acc[tp + 1] = NCW_MFMA_H(w[q], f[1], acc[tp + 1], 0, 0, 0);
+        if (NB == 2) {
+            acc[tp] = NCW_MFMA_H(w[q], f[2], acc[tp], 0, 0, 0);
+            acc[tp + 1] = NCW_MFMA_H(w[q], f[3], acc[tp + 1], 0, 0, 0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// the epilogue of one output block of NT tiles (first tile t0): ReLU (or none: f), the stash block, hi / lo fragments in place
+template <int NT, bool RELU, bool TRAIN>
+NCW_DEV void cw_epilogue(const f32x16 (&acc)[NT], ss_lfrag* abuf, ncw_h16* __restrict__ st, size_t tile0, int t0, int RB, int ob,
+                         int lane) {
+    ncw_lds_barrier();  // every wave has finished reading the layer input
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        f32x16 y;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) y[r] = RELU ? ncw_relu(acc[t][r]) : acc[t][r];
+        if (TRAIN) stash_store_block(st, tile0 + t0 + t, RB, ob, y, lane);
+        ns_store(abuf, t0 + t, ob, y, lane);
+    }
+    ncw_lds_barrier();  // the layer output is complete
+}
+
+// acc[t] = the bias block, as NT copies made HERE: handed the one block, hipcc feeds it to the first MFMA of every tile as its C
+// operand and keeps its 16 registers alive through half of the pass beside the accumulators (the 256-wide layers then spill)
+template <int NT>
+NCW_DEV void cw_init(f32x16 (&acc)[NT], const f32x16& bias) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        acc[t] = bias;
+        asm volatile("" : "+v"(acc[t]));
+    }
+}
+
+// build_aux1<true> (ncw_mlp.h) with the view direction passed BY VALUE: given the array, the component select of freq_feature
+// is compiled as an indexed load from a private copy of it -- 16 B of scratch per lane (ss_gamma_deriv above).  Same arithmetic.
+NCW_DEV float cw_dir_feature(float d0, float d1, float d2, int f) {  // freq_feature<3, 4, true>
+    if (f < 3) return f == 2 ? d2 : (f == 1 ? d1 : d0);
+    if (f >= 27) return 0.f;
+    const int j = f - 3;
+    const int k = j / 6;
+    const int rem = j - k * 6;
+    const bool is_cos = rem >= 3;
+    const int comp = is_cos ? rem - 3 : rem;
+    const float v = comp == 2 ? d2 : (comp == 1 ? d1 : d0);
+    const float arg = v * (float)(1 << k);
+    const float rev = arg * 0.15915494309189535f;  // revolutions
+    return is_cos ? __builtin_amdgcn_cosf(rev) : __builtin_amdgcn_sinf(rev);
+}
+NCW_DEV void cw_build_aux1(CVec<3>& aux, float d0, float d1, float d2, const float* __restrict__ a_row, int n_a, int lane) {
+    const int h = lane >> 5;
+    // a_row[f - 27] or 0 beyond n_a, as an UNCONDITIONAL load from a clamped index (n_a > 0: wave-uniform) and a select: under
+    // the per-lane condition every element is a branch of its own with a vmcnt(0) behind it, ~40 dependent round trips per tile
+    auto av = [&](int f) {
+        if (n_a <= 0) return 0.f;
+        const bool in = f - 27 < n_a;
+        const float t = a_row[in ? f - 27 : 0];
+        return in ? t : 0.f;
+    };
+#pragma unroll
+    for (int rb = 0; rb < 3; ++rb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int f = 32 * rb + ncw_feat_of(r, 0) + 4 * h;
+            float v;
+            if (32 * rb + ncw_feat_of(r, 0) + 4 < 27) {  // both halves inside the direction encoding
+                v = cw_dir_feature(d0, d1, d2, f);
+            } else if (32 * rb + ncw_feat_of(r, 0) >= 27) {  // both halves in the embedding / padding
+                v = av(f);
+            } else {
+                v = (f < 27) ? cw_dir_feature(d0, d1, d2, f) : av(f);
+            }
+            aux.v[rb][r] = v;
+        }
+}
+
+NCW_DEV int64_t cw_ray_of(const NcwPoints& s, int64_t p) { return (s.mode == 0 || s.mode == 3) ? p : p / s.per_ray; }  // (load_point)
+
+template <bool TRAIN>
+__global__ __launch_bounds__(64 * SS_WAVES) void color_fwdS_kernel(NcwColorNet net, NcwPoints src, int64_t n,
+                                                                  const float* __restrict__ normals, const float* __restrict__ a,
+                                                                  const void* __restrict__ feat_stash, float* __restrict__ rgb,
+                                                                  NcwColorStash st) {
+    typedef ncw_h16 SE;
+    __shared__ __attribute__((aligned(16))) char lds[SS_ACT + CW_X1 + CW_X2];
+    ss_lfrag* const abuf = (ss_lfrag*)(ncw_lchar*)lds;
+    ss_lfrag* const x1buf = abuf + SS_ACT / 16;
+    ss_lfrag* const x2buf = x1buf + CW_X1 / 16;
+    const int lane = ncw_lane();
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int64_t tile0 = (int64_t)blockIdx.x * SS_TILES;
+    const int hb = wave & 3, ht = wave >> 2;  // the head: block hb of tiles 2 ht, 2 ht + 1
+    const int last = net.n_lin - 1;
+    const bool rows = st.aux_bias != nullptr;  // per-ray fp32 head rows: no AUX1 operand
+    bf16x8 Wh[16], Wl[16];  // the HI and the LO register set of the current slice
+    cw_load<16>(Wh, net.w_f, 8, wave, lane);
+    cw_load<16>(Wl, net.w_f_lo, 8, wave, lane);
+    f32x16 bnext = ss_bias(net.b_f, wave, lane);  // the next layer's bias block, requested one epilogue ahead (ss_value_chain)
+    // ---- inputs: feat (block `wave` of the four tiles: the stash holds the B fragments' bits), AUX1 (wave t: tile t), AUX2
+    // (wave 4 + t: tile t) ----------------------------------------------------------------------------------------------------
+    {
+#pragma unroll
+        for (int t = 0; t < SS_TILES; ++t) {
+            const bf16x4* fp = reinterpret_cast<const bf16x4*>(feat_stash) + (((size_t)(tile0 + t) * 8 + wave) * 4) * 64 + lane;
+            bf16x4 g[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) g[i] = NCW_STASH_LD(fp[i * 64]);
+#pragma unroll
+            for (int tt = 0; tt < 2; ++tt) {  // unit 2 wave + tt = registers 8 tt .. 8 tt + 7 = pieces 2 tt, 2 tt + 1
+                bf16x8 f;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) { f[e] = g[2 * tt][e]; f[4 + e] = g[2 * tt + 1][e]; }
+                abuf[((t * 16 + 2 * wave + tt) * 2) * 64 + lane] = f;
+            }
+        }
+        const int jt = wave & 3;
+        int64_t p = (tile0 + jt) * 32 + (lane & 31), ray;
+        if (p >= n) p = n - 1;  // padded lanes: the clamped point (tile_setup)
+        float xs[3];
+        load_point(src, p, xs, ray);
+        if (wave < SS_TILES) {
+            if (TRAIN || !rows) {
+                const float d0 = src.rays_d[ray * 3 + 0], d1 = src.rays_d[ray * 3 + 1], d2 = src.rays_d[ray * 3 + 2];
+                CVec<3> aux1;
+                cw_build_aux1(aux1, d0, d1, d2, a + ray * net.n_a, net.n_a, lane);
+                if (TRAIN) stash_store<3>((SE*)st.aux1, (size_t)(tile0 + jt), aux1, lane);
+                Act<PrecBF16, 3> a1;
+                to_act(a1, aux1);
+#pragma unroll
+                for (int q = 0; q < 6; ++q) x1buf[(jt * 6 + q) * 64 + lane] = a1.f[q];
+            }
+        } else {
+            const float nrm[3] = {normals[p * 3 + 0], normals[p * 3 + 1], normals[p * 3 + 2]};
+            CVec<1> aux2;
+            build_aux2(aux2, xs, nrm, lane);
+            if (TRAIN) stash_store<1>((SE*)st.aux2, (size_t)(tile0 + jt), aux2, lane);
+            bf16x8 hi, lo;
+            ss_split8(aux2.v[0], 0, hi, lo);
+            x2buf[(jt * 2 + 0) * 64 + lane] = hi;
+            x2buf[(jt * 2 + 1) * 64 + lane] = lo;
+        }
+    }
+    const ss_lfrag* const ain = abuf + lane;
+    const ss_lfrag* const hin = ain + 2 * ht * CW_TILE;
+    f32x16 acc[SS_TILES], hacc[2];
+    // ---- f = xyz_encoding_final(feat): single-rounded input, W_hi over all units, then W_lo; no activation ------------------
+    {
+        cw_init<SS_TILES>(acc, bnext);
+        ncw_lds_barrier();  // the inputs are visible
+        cw_mma<SS_TILES, 16, 1, CW_TILE, 128>(acc, Wh, ain);
+        cw_load<16>(Wh, net.w_e[0], 4, hb, lane);
+        cw_mma<SS_TILES, 16, 1, CW_TILE, 128>(acc, Wl, ain);
+        // the head's first bias block and this wave's two per-ray rows, requested ahead of the epilogue
+        bnext = ss_bias(net.b_e[0], hb, lane);
+        f32x4 rr[2][4];
+        if (rows) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                int64_t p = (tile0 + 2 * ht + j) * 32 + (lane & 31);
+                if (p >= n) p = n - 1;
+                const f32x4* ab = reinterpret_cast<const f32x4*>(st.aux_bias + cw_ray_of(src, p) * 128) + 8 * hb + (lane >> 5);
+#pragma unroll
+                for (int g = 0; g < 4; ++g) rr[j][g] = ab[2 * g];  // (ncw_add_ray_bias_block)
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int g = 0; g < 4; ++g) rr[j][g] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        cw_epilogue<SS_TILES, false, TRAIN>(acc, abuf, (SE*)st.f, (size_t)tile0, 0, 8, wave, lane);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            hacc[j] = bnext;
+            if (rows) {
+#pragma unroll
+                for (int r = 0; r < 16; ++r) hacc[j][r] += rr[j][r >> 2][r & 3];
+            }
+        }
+    }
+    // ---- appearance head, layer 0: K = [f (16 units, pairs) | AUX1 (6 units, hi only; none with the per-ray rows)] ---------
+    {
+        cw_load<16>(Wl, net.w_e_lo[0], 4, hb, lane);
+        cw_mma<2, 16, 2, CW_TILE, 128>(hacc, Wh, hin);
+        if (!rows) {
+            bf16x8 xw[16];
+            cw_load<6>(xw, (const char*)net.w_e[0] + (size_t)16 * 4 * 1024, 4, hb, lane);
+            cw_mma<2, 6, 1, 6 * 64, 64>(hacc, xw, x1buf + 2 * ht * 6 * 64 + lane);
+        }
+        const bool more = net.n_head > 1;
+        cw_load<8>(Wh, more ? net.w_e[1] : net.w_l[0], more ? 4 : 8, more ? hb : wave, lane);
+        cw_mma<2, 16, 1, CW_TILE, 128>(hacc, Wl, hin);
+        if (!rows) {
+            bf16x8 xw[16];
+            cw_load<6>(xw, (const char*)net.w_e_lo[0] + (size_t)16 * 4 * 1024, 4, hb, lane);
+            cw_mma<2, 6, 1, 6 * 64, 64>(hacc, xw, x1buf + 2 * ht * 6 * 64 + lane);
+        }
+        bnext = ss_bias(more ? net.b_e[1] : net.b_l[0], more ? hb : wave, lane);
+        cw_epilogue<2, true, TRAIN>(hacc, abuf, (SE*)st.e[0], (size_t)tile0, 2 * ht, 4, hb, lane);
+    }
+    for (int i = 1; i < net.n_head; ++i) {
+        cw_load<8>(Wl, net.w_e_lo[i], 4, hb, lane);
+        cw_init<2>(hacc, bnext);
+        cw_mma<2, 8, 2, CW_TILE, 128>(hacc, Wh, hin);
+        const bool more = i + 1 < net.n_head;
+        cw_load<8>(Wh, more ? net.w_e[i + 1] : net.w_l[0], more ? 4 : 8, more ? hb : wave, lane);
+        cw_mma<2, 8, 1, CW_TILE, 128>(hacc, Wl, hin);
+        bnext = ss_bias(more ? net.b_e[i + 1] : net.b_l[0], more ? hb : wave, lane);
+        cw_epilogue<2, true, TRAIN>(hacc, abuf, (SE*)st.e[i], (size_t)tile0, 2 * ht, 4, hb, lane);
+    }
+    // ---- trunk layer 0: K = [e (8 units) | unit 0 of AUX2 = points, normals], all pairs -----------------------------------------
+    // the slice that follows a trunk layer: the next 256-wide one, or the rgb row (1 block: every wave loads it, waves 0..3 use it)
+    {
+        const ss_lfrag* const x2in = x2buf + lane;
+        bf16x8 w8[16];
+        cw_load<8>(Wl, net.w_l_lo[0], 8, wave, lane);
+        cw_load<1>(w8, (const char*)net.w_l[0] + (size_t)8 * 8 * 1024, 8, wave, lane);
+        cw_init<SS_TILES>(acc, bnext);
+        cw_mma<SS_TILES, 8, 2, CW_TILE, 128>(acc, Wh, ain);
+        cw_mma<SS_TILES, 1, 2, 2 * 64, 128>(acc, w8, x2in);
+        const bool more = 1 < last;
+        cw_load<16>(Wh, more ? net.w_l[1] : net.w_l[last], more ? 8 : 1, more ? wave : 0, lane);
+        cw_load<1>(w8, (const char*)net.w_l_lo[0] + (size_t)8 * 8 * 1024, 8, wave, lane);
+        cw_mma<SS_TILES, 8, 1, CW_TILE, 128>(acc, Wl, ain);
+        cw_mma<SS_TILES, 1, 1, 2 * 64, 128>(acc, w8, x2in);
+        bnext = ss_bias(net.b_l[more ? 1 : 0], wave, lane);
+        cw_epilogue<SS_TILES, true, TRAIN>(acc, abuf, (SE*)st.x[0], (size_t)tile0, 0, 8, wave, lane);
+    }
+    // ---- trunk layers 1 .. last - 1 -------------------------------------------------------------------------------------------
+    for (int l = 1; l < last; ++l) {
+        cw_load<16>(Wl, net.w_l_lo[l], 8, wave, lane);
+        cw_init<SS_TILES>(acc, bnext);
+        cw_mma<SS_TILES, 16, 2, CW_TILE, 128>(acc, Wh, ain);
+        const bool more = l + 1 < last;
+        cw_load<16>(Wh, more ? net.w_l[l + 1] : net.w_l[last], more ? 8 : 1, more ? wave : 0, lane);
+        cw_mma<SS_TILES, 16, 1, CW_TILE, 128>(acc, Wl, ain);
+        bnext = ss_bias(net.b_l[more ? l + 1 : l], wave, lane);  // (one form: the last layer asks for its own again)
+        cw_epilogue<SS_TILES, true, TRAIN>(acc, abuf, (SE*)st.x[l], (size_t)tile0, 0, 8, wave, lane);
+    }
+    // ---- rgb row (1 output block), tile t by wave t; sigmoid (neuconw.py:168-169) ----------------------------------------------
+    if (wave < SS_TILES) {
+        cw_load<16>(Wl, net.w_l_lo[last], 1, 0, lane);
+        CVec<1> o;
+        load_bias(o, net.b_l[last], lane);
+        const ss_lfrag* in = ain + wave * CW_TILE;
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const bf16x8 bh = in[q * 128], bl = in[q * 128 + 64];
+            o.v[0] = NCW_MFMA_H(Wh[q], bh, o.v[0], 0, 0, 0);
+            o.v[0] = NCW_MFMA_H(Wh[q], bl, o.v[0], 0, 0, 0);
+        }
+#pragma unroll
+        for (int q = 0; q < 16; ++q) o.v[0] = NCW_MFMA_H(Wl[q], in[q * 128], o.v[0], 0, 0, 0);
+        const int64_t p = (tile0 + wave) * 32 + (lane & 31);
+        if (p < n && lane < 32) {  // features 0,1,2 <-> registers 0,1,2 of half 0
+            rgb[p * 3 + 0] = sigmoidf_<true>(o.v[0][0]);
+            rgb[p * 3 + 1] = sigmoidf_<true>(o.v[0][1]);
+            rgb[p * 3 + 2] = sigmoidf_<true>(o.v[0][2]);
+        }
+    }
+}
+
 }  // namespace
 
 // Measured per 131,072 points on MI355X (scripts/diag/split_check.py; plain fp16 kernels: 0.160 / 0.558 ms):
@@ -1131,6 +1461,18 @@ int ncw_nerf_refineS_launch_f16(const NcwNerfNet* net, const NcwPoints& src, int
     const int64_t tiles = (n + 31) / 32;
     hipLaunchKernelGGL(nerf_refineS_kernel, dim3((unsigned)((tiles + NS_TILES - 1) / NS_TILES)), dim3(64 * NS_WAVES), 0, st, *net, src,
                        n, aux_bias, density, rgb);
+    NCW_CHECK_LAUNCH();
+    return 0;
+}
+
+// ncw_color_fwd at (fp16, key 80408, weights and activations as pairs): the weights-stationary kernel; same grid as the generic one
+int ncw_color_fwdS_launch_f16(const NcwColorNet* net, const NcwPoints& src, int64_t n, const float* normals, const float* a,
+                              const void* feat_stash, float* rgb, const NcwColorStash& stash, hipStream_t st) {
+    const int64_t tiles = (n + 31) / 32;
+    const dim3 grid((unsigned)((tiles + SS_TILES - 1) / SS_TILES));
+    const bool render = stash.aux1 == nullptr;  // forward-only render (include/neuconw_hip.h, NcwColorStash)
+    if (render) hipLaunchKernelGGL(color_fwdS_kernel<false>, grid, dim3(64 * SS_WAVES), 0, st, *net, src, n, normals, a, feat_stash, rgb, stash);
+    else hipLaunchKernelGGL(color_fwdS_kernel<true>, grid, dim3(64 * SS_WAVES), 0, st, *net, src, n, normals, a, feat_stash, rgb, stash);
     NCW_CHECK_LAUNCH();
     return 0;
 }

@@ -361,10 +361,14 @@ class RenderingNetwork(_PackedNet):
         # NEUCONW_COLOR_ASPLIT=0 / 1 or `.act_split = False / True` override.
         env = os.environ.get("NEUCONW_COLOR_ASPLIT")
         self.act_split = None if env is None else (env not in ("0", ""))
+        # fp16 mode, act_split at d_feature = 256 / head 128 / trunk 256: the forward runs the weights-stationary kernel (csrc/ncw_split.hip
+        # color_fwdS_kernel: eight waves per workgroup, the same bits).  NEUCONW_COLOR_WS=0 / `.ws_forward = False` = the pairs through the
+        # generic register-resident kernel (NcwColorNet.act_split = 2): for bisecting, and what tests/test_gpu_color_fwd_ws.py compares with
+        self.ws_forward = os.environ.get("NEUCONW_COLOR_WS", "1") != "0"
         self._init_plans()
 
     def _plan_switches(self, prec):
-        return (bool(self.weight_split), self.act_split)
+        return (bool(self.weight_split), self.act_split, bool(self.ws_forward))
 
     @property
     def n_lin(self):
@@ -401,7 +405,7 @@ class RenderingNetwork(_PackedNet):
             net.w_l_lo[l] = plan.mat_ptr(s.lo)
         net.n_head, net.n_lin, net.rbf, net.rbh, net.rbc, net.n_a = self.n_head, self.n_lin, RBF, RBH, RBC, A
         asplit = True if self.act_split is None else bool(self.act_split)
-        net.act_split = 1 if (split and asplit and (RBF, RBH, RBC) in ((8, 4, 8), (16, 4, 8))) else 0
+        net.act_split = (1 if self.ws_forward else 2) if (split and asplit and (RBF, RBH, RBC) in ((8, 4, 8), (16, 4, 8))) else 0
         plan.net, plan.slots = net, sl
         return plan
 
