@@ -816,6 +816,66 @@ int ncw_image_ssim(const float* pred, const float* gt, int channels, int height,
                    float* ssim_out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Surface views by sphere tracing (csrc/ncw_trace.hip; not in the reference): the per-ray march that finds the first point with
+ * |sdf| <= eps along o + t d, t in [near, far], |d| = 1.  The SDF itself is evaluated BETWEEN these launches by the value path
+ * (ncw_sdf_infer) on the points they emit.  Everything is float32 with every product, quotient and sum rounded once (no FMA
+ * contraction, IEEE division), so that a numpy float32 restatement reproduces it bit for bit (tests/_trace_ref.py).
+ *
+ *   state = ACTIVE if far > near else MISS (0 evaluations);  t = near;  bracketed = 0
+ *   each evaluation k = 1, 2, ...:  p = o + t d (mul, then add, per component);  s = sdf(p);  iters += 1
+ *     s not finite -> STALLED;   |s| <= eps -> HIT (depth t);   s > 0 -> t_lo = t, s_lo = s;
+ *     s < 0: k == 1 -> INSIDE (the interval starts below the surface);  else t_hi = t, s_hi = s, bracketed = max(bracketed, 1)
+ *     not bracketed:  t' = t + step s;  t' > far -> MISS;  else t = t'
+ *     bracketed:      w = t_hi - t_lo;  odd count: t = t_lo + (s_lo w) / (s_lo - s_hi) (false position);
+ *                     even count: t = t_lo + 0.5 w (bisection);  bracketed += 1
+ *     iters == max_iter and still ACTIVE -> STALLED
+ *
+ * The bracket keeps the walk convergent where |grad sdf| > 1 (plain t += s stalls or oscillates there).  It cannot find a surface
+ * the walk jumped over entirely (both crossings inside one step: possible only where |grad sdf| step > 1); step < 1 is for that.
+ *
+ * rec [R][NCW_TRACE_REC_WORDS] 32-bit words per ray: t, t_lo, s_lo, t_hi, s_hi (f32) and one packed word: bits 0-3 the state
+ * (0 ACTIVE, NCW_TRACE_*), bits 4-17 the bracket count, bits 18-31 iters (hence max_iter <= NCW_TRACE_MAX_ITER).
+ * An ACTIVE LIST is ray indices int32 [m], ASCENDING, with its length in a DEVICE int32 `count`; its points [m][3] are o + t d of
+ * the listed rays in list order.  Lists are compacted order-preserving by a two-stage fixed-order scan (per-workgroup counts in
+ * `scratch`, ncw_trace_scratch_bytes(R) bytes, at least 4-byte aligned): no atomics of any kind, bitwise reproducible.
+ *
+ *   ncw_trace_begin : initialises rec for R rays (rays_o / rays_d [R][3], near / far [R]) and writes the first active list
+ *                     (the rays with far > near), *count and its points.
+ *   ncw_trace_step  : consumes sdf [m] of the list (active_in, *count_in): updates rec by one evaluation of the recurrence above
+ *                     and writes the list of the rays still ACTIVE (active_out, *count_out) and their next points.  m_bound is an
+ *                     UPPER BOUND of *count_in known to the host (the grid size); the kernels read the count itself from the
+ *                     device, so the host may read it back as rarely as it likes.  Entries of sdf / points past the count are
+ *                     ignored / left alone.  active_out / count_out must not alias active_in / count_in.
+ *   ncw_trace_finish: unpacks rec into t [R] (HIT: the hit depth; INSIDE: near; otherwise the last depth of the recurrence),
+ *                     state [R] uint8, iters [R] int32 and points [R][3] = o + t d; each output may be NULL.
+ *   ncw_trace_store : one chunk of n pixels at offset p0 into the planes of a view of n_pix pixels (layout of ncw_view_store):
+ *                     depth_img = t at a HIT and 0 elsewhere, state_img uint8, iters_img int32; colour and normal planes get
+ *                     background[3] (HOST floats) and 0 at every pixel, then rgb [n_hit][3] and g / |g| / 2 + 0.5 of grad [n_hit][3]
+ *                     at the pixels p0 + hit_idx[j] (int64, ascending, each a HIT of this chunk).  n_hit == 0: no second launch.
+ *
+ * All return NCW_E_BADARG without a launch for a NULL or misaligned (4 bytes; hit_idx 8) pointer, R / m_bound / n outside
+ * [0, 2^31 - 1], m_bound > R, eps <= 0, step outside (0, 1], max_iter outside [1, NCW_TRACE_MAX_ITER] (NaNs included) or a
+ * range outside the view; 0 without a launch for R == 0 (begin: *count is then NOT written), m_bound == 0 and n == 0.
+ * ---------------------------------------------------------------------------------------- */
+#define NCW_TRACE_HIT 1
+#define NCW_TRACE_MISS 2
+#define NCW_TRACE_INSIDE 3
+#define NCW_TRACE_STALLED 4
+#define NCW_TRACE_REC_WORDS 6
+#define NCW_TRACE_MAX_ITER 16383
+int64_t ncw_trace_scratch_bytes(int64_t R);
+int ncw_trace_begin(const float* rays_o, const float* rays_d, const float* near, const float* far, int64_t R, float* rec,
+                    int32_t* active, int32_t* count, float* points, void* scratch, void* stream);
+int ncw_trace_step(const float* sdf, const int32_t* active_in, const int32_t* count_in, int64_t m_bound, const float* rays_o,
+                   const float* rays_d, const float* far, int64_t R, float eps, float step, int max_iter, float* rec,
+                   int32_t* active_out, int32_t* count_out, float* points, void* scratch, void* stream);
+int ncw_trace_finish(const float* rec, const float* rays_o, const float* rays_d, int64_t R, float* t, uint8_t* state,
+                     int32_t* iters, float* points, void* stream);
+int ncw_trace_store(const float* t, const uint8_t* state, const int32_t* iters, const int64_t* hit_idx, const float* rgb,
+                    const float* grad, int64_t n_hit, const float* background_host, int64_t p0, int64_t n, int64_t n_pix,
+                    float* color_img, float* depth_img, float* normal_img, uint8_t* state_img, int32_t* iters_img, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Ray cache (csrc/ncw_cache.hip): the training rows of ONE image as the reference's dataset builds them for
  * tools/prepare_data/prepare_data_cache.py (datasets/phototourism.py:150-209, 557-657), without its host round trips.
  *   ncw_sfm_depth_splat : get_colmap_depth (:150-209) without the dir_norm factor (ncw_cache_rows applies it): the n SfM

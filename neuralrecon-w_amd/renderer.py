@@ -459,13 +459,7 @@ class NeuconWRenderer:
         dev = rays_o.device
         R = rays_o.shape[0]
         rays_o, rays_d = rays_o.contiguous().float(), rays_d.contiguous().float()
-        if self.nerf_far_override if far_override is None else far_override:
-            if self.octree_data is None:
-                self.octree_data = self.get_octree(dev)
-            near, far, _ = self.get_near_far_octree(self.octree_data, rays_o, rays_d, near, far)
-        s_near, s_far = near, far
-        if self.fine_octree_data is not None:
-            s_near, s_far, _ = self.get_near_far_sdf(self.fine_octree_data, rays_o, rays_d, near, far)
+        near, far, s_near, s_far = self.ray_intervals(rays_o, rays_d, near, far, far_override)
         n_out = self.n_outside if (self.render_bg and self.n_outside > 0) else 0
         rs = ro = None
         if perturb > 0:
@@ -489,6 +483,22 @@ class NeuconWRenderer:
         return n_samples, z, z_out, sample_dist
 
     # ---- voxel guidance (renderer.py:137-155, 380-456): see voxel.py ---------------------------------
+    @torch.no_grad()
+    def ray_intervals(self, rays_o, rays_d, near, far, far_override=None):
+        """The depth intervals of the sampler (renderer.py:470-486), shared by `sparse_sampler` and the sphere tracer (trace.py):
+        returns (near, far, s_near, s_far).  [near, far] are the rays' own, replaced by the SfM octree's where it is hit under
+        `nerf_far_override` (far_override: None = that attribute; True / False decide it for this call); [s_near, s_far] is the
+        surface interval: `get_near_far_sdf`'s band around the fine octree's first hit when `fine_octree_data` is set (rays that
+        miss it keep near / far), else near / far themselves."""
+        if self.nerf_far_override if far_override is None else far_override:
+            if self.octree_data is None:
+                self.octree_data = self.get_octree(rays_o.device)
+            near, far, _ = self.get_near_far_octree(self.octree_data, rays_o, rays_d, near, far)
+        s_near, s_far = near, far
+        if self.fine_octree_data is not None:
+            s_near, s_far, _ = self.get_near_far_sdf(self.fine_octree_data, rays_o, rays_d, near, far)
+        return near, far, s_near, s_far
+
     def get_octree(self, device):
         from . import voxel
 
@@ -562,6 +572,25 @@ class NeuconWRenderer:
         ps += [p for n, p in nf.named_parameters() if not n.startswith("views_linears")]
         return ps
 
+    def ray_prologue(self, rays):
+        """renderer.py:793-806 (ray normalisation into unit-sphere units) as one launch: rays [R, >= 8] on the device ->
+        rays_o [R,3], rays_d [R,3], near [R,1], far [R,1], depth_gt [R], depth_weight [R].  Shared by render() and trace.py."""
+        device = rays.device
+        if self.origin.device != device:
+            self.origin = self.origin.to(device).float()
+            self.sfm_to_gt = self.sfm_to_gt.to(device).float()
+        R = rays.shape[0]
+        rays_c = rays.contiguous().float()
+        rays_o, rays_d = torch.empty(R, 3, device=device), torch.empty(R, 3, device=device)
+        near, far = torch.empty(R, 1, device=device), torch.empty(R, 1, device=device)
+        depth_gt, depth_weight = torch.empty(R, device=device), torch.empty(R, device=device)
+        if self.__dict__.get("_origin_host") is None or self._origin_host[1] is not self.origin:
+            self._origin_host = ((C.c_float * 3)(*[float(v) for v in self.origin.reshape(-1).tolist()]), self.origin)
+        L.check(L.get_lib().ncw_ray_prologue(L.ptr(rays_c), rays_c.shape[1], R, self._origin_host[0], float(self.radius),
+                                             L.ptr(rays_o), L.ptr(rays_d), L.ptr(near), L.ptr(far), L.ptr(depth_gt),
+                                             L.ptr(depth_weight), L.stream_ptr(device)), "ncw_ray_prologue")
+        return rays_o, rays_d, near, far, depth_gt, depth_weight
+
     def render(self, rays, ts, label, perturb_overwrite=-1, background_rgb=None, cos_anneal_ratio=0.0, _rand=None, _z_override=None):
         """_rand / _z_override are test hooks: the sampler's uniforms, and primary sample depths [R, S] that replace the sampler's
         (parity of the MLPs + compositor at FIXED sample positions, bench.py `parity.fixed_z`)."""
@@ -585,17 +614,8 @@ class NeuconWRenderer:
         if self.__dict__.get("sampler_prec") is None:
             nets = [self.neuconw.sdf_net, self.neuconw.color_net] + ([self.nerf] if (self.render_bg and self.n_outside > 0) else [])
             pack_many([(m, m.plan(self.prec)) for m in nets])
-        # renderer.py:793-806 (ray normalisation into unit-sphere units) as one launch
         R = rays.shape[0]
-        rays_c = rays.contiguous().float()
-        rays_o, rays_d = torch.empty(R, 3, device=device), torch.empty(R, 3, device=device)
-        near, far = torch.empty(R, 1, device=device), torch.empty(R, 1, device=device)
-        depth_gt, depth_weight = torch.empty(R, device=device), torch.empty(R, device=device)
-        if self.__dict__.get("_origin_host") is None or self._origin_host[1] is not self.origin:
-            self._origin_host = ((C.c_float * 3)(*[float(v) for v in self.origin.reshape(-1).tolist()]), self.origin)
-        L.check(L.get_lib().ncw_ray_prologue(L.ptr(rays_c), rays_c.shape[1], R, self._origin_host[0], float(self.radius),
-                                             L.ptr(rays_o), L.ptr(rays_d), L.ptr(near), L.ptr(far), L.ptr(depth_gt),
-                                             L.ptr(depth_weight), L.stream_ptr(device)), "ncw_ray_prologue")
+        rays_o, rays_d, near, far, depth_gt, depth_weight = self.ray_prologue(rays)
         emb_a = self.embeddings["a"]
         ordered = self.reproducible if self.reproducible is not None else (self.prec == L.PREC_F32)
         if a_code is not None:

@@ -8,6 +8,8 @@
 The rays of a pixel chunk are generated on the device (`ncw_view_rays`), rendered by the forward-only render
 (renderer.NeuconWRenderer under no_grad) and scattered into planar images (`ncw_view_store`); depth colour map and metrics are
 `ncw_image_*` / `ncw_depth_colormap` launches (csrc/ncw_view.hip).  Nothing is copied to the host per chunk.
+
+    out = trace_view(rdr, cam, ts=image_id, gt=gt.cuda())           # the SURFACE instead: sphere tracing (trace.py), colour / normal at the first hit
 """
 import ctypes as C
 import os
@@ -225,6 +227,97 @@ def render_view(rdr, camera, ts, chunk=DEFAULT_CHUNK, gt=None, label=None, backg
         if min(H, W) > (ssim_window - 1) // 2:
             res["ssim"] = ssim(color, g, ssim_window)
         else:  # SSIM is undefined below the window's reflect padding
+            res["ssim"] = torch.full((), float("nan"), device=device)
+    return res
+
+
+TRACE_CHUNK = 1 << 17  # rays per trace_rays call of trace_view (scripts/bench_trace.py measures the chunk size: profiles/trace/README.md)
+
+
+def trace_view(rdr, camera, ts, *, chunk=TRACE_CHUNK, background_rgb=None, a_code=None, gt=None, shade=True, ssim_window=3,
+               device=None, shade_prec=None, **trace_kw):
+    """The surface of one whole view by sphere tracing (trace.py; not in the reference): per chunk `ncw_view_rays` ->
+    trace.trace_rays -> `NeuconW.forward([p, d, a])` over the rays that HIT (ascending ray index) -> `ncw_trace_store`.
+    No background NeRF and no transmittance: a pixel shows the colour network's answer AT the first surface point, or
+    background_rgb (3 values, default 0) where the ray found none.  ts / a_code: the appearance as in render_view.
+    Returns device tensors color [3,H,W], depth [H,W] (t at a hit, render_view's units; 0 elsewhere), normal [3,H,W]
+    (g / |g| / 2 + 0.5 at a hit, 0 elsewhere), state [H,W] uint8 (trace.HIT / MISS / INSIDE / STALLED), iters [H,W] int32,
+    depth_vis [3,H,W] and `stats` (host numbers: pixels per state, mean / max iters, SDF launches and evaluated points, forward
+    launches); with gt also mse / psnr / ssim over the image as render_view computes them and psnr_hit over the hit pixels.
+    shade=False skips the forward (colour stays background, normal 0).  shade_prec: precision of the forward (None = the
+    renderer's `infer_prec` or fp32, as NeuconWRenderer.rgb); trace_kw goes to trace_rays (eps, max_iter, step, far_override,
+    sdf_fn, sync_every, prec)."""
+    from . import trace as T
+    from .neuconw import default_infer_prec
+
+    H, W = camera.height, camera.width
+    hw = H * W
+    chunk = max(1, min(int(chunk), hw))
+    if device is None:
+        device = next(rdr.neuconw.parameters()).device
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise L.NeuconwHipError("views.trace_view: the renderer is not on a GPU; the hot path has no CPU fallback")
+    bg = [0.0, 0.0, 0.0]
+    if background_rgb is not None:
+        if torch.as_tensor(background_rgb).numel() != 3:
+            raise ValueError("trace_view: background_rgb must hold ONE colour (3 values)")
+        bg = [float(v) for v in torch.as_tensor(background_rgb).reshape(3).tolist()]
+    lib = L.get_lib()
+    cam = camera.struct()
+    planes = {"color": torch.empty(3, H, W, device=device, dtype=torch.float32),
+              "depth": torch.empty(H, W, device=device, dtype=torch.float32),
+              "normal": torch.empty(3, H, W, device=device, dtype=torch.float32),
+              "state": torch.empty(H, W, device=device, dtype=torch.uint8),
+              "iters": torch.empty(H, W, device=device, dtype=torch.int32)}
+    rays = torch.empty(chunk, 8, device=device, dtype=torch.float32)
+    if shade_prec is None:
+        shade_prec = default_infer_prec() if rdr.infer_prec is None else rdr.infer_prec
+    launches = evaluated = forwards = 0
+    with torch.no_grad():
+        if a_code is not None:
+            if not a_code.is_cuda:
+                raise L.NeuconwHipError("views.trace_view: a_code is not on a GPU; the hot path has no CPU fallback")
+            a_row = a_code.detach().reshape(1, -1).float()
+        else:
+            a_row = rdr.embeddings["a"](torch.full((1,), int(ts), device=device, dtype=torch.int64)).detach().float()
+        for p0 in range(0, hw, chunk):
+            n = min(chunk, hw - p0)
+            r = rays[:n]
+            L.check(lib.ncw_view_rays(C.byref(cam), p0, n, L.ptr(r), L.stream_ptr(device)), "ncw_view_rays")
+            tr = T.trace_rays(rdr, r, **trace_kw)
+            launches += tr["launches"]
+            evaluated += tr["evaluated"]
+            hit = rgb = grad = None
+            if shade:
+                hit = torch.nonzero(tr["state"] == T.HIT).reshape(-1)  # ascending; its length reaches the host here
+                if hit.numel() > 0:
+                    h = hit.numel()
+                    x = torch.cat([tr["points"][hit], r[hit, 3:6], a_row.expand(h, -1)], 1).unsqueeze(1)
+                    rgb, _, _, grad = rdr.neuconw(x, shade_prec)
+                    forwards += 1
+                else:
+                    hit = None
+            T.store_chunk(planes, p0, tr, hit, rgb, grad, bg)
+    res = dict(planes)
+    res["depth_vis"] = depth_colormap(planes["depth"])
+    cnt = torch.bincount(planes["state"].reshape(-1).long(), minlength=5).tolist()
+    it = planes["iters"]
+    res["stats"] = {"rays": hw, "hit": cnt[T.HIT], "miss": cnt[T.MISS], "inside": cnt[T.INSIDE], "stalled": cnt[T.STALLED],
+                    "iters_mean": float(it.float().mean()), "iters_max": int(it.max()), "sdf_launches": launches,
+                    "sdf_points": evaluated, "forward_launches": forwards}
+    if gt is not None:
+        g = gt.to(device).float()
+        if g.dim() == 2:  # [H * W, 3], the dataset's layout
+            g = g.reshape(H, W, 3).permute(2, 0, 1)
+        g = g.reshape(3, H, W).contiguous()
+        s, c = sqerr(planes["color"], g)
+        res["mse"] = (s / c.float()).reshape(())
+        res["psnr"] = -10.0 * torch.log10(res["mse"])
+        res["psnr_hit"] = psnr(planes["color"], g, planes["state"] == T.HIT)
+        if min(H, W) > (ssim_window - 1) // 2:
+            res["ssim"] = ssim(planes["color"], g, ssim_window)
+        else:
             res["ssim"] = torch.full((), float("nan"), device=device)
     return res
 
