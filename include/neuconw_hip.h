@@ -1392,6 +1392,94 @@ int ncw_align_sums(const double* src, int64_t n, const double* cp, const double*
                    const int64_t* idx, const float* dist, float gate, const double* T, double* part, int64_t* ipart,
                    double* sums, int64_t* counts, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Fusing traced surface samples into one surface cloud (csrc/ncw_fuse.hip; surfcloud.SurfaceCloud / fuse_views): the hits of
+ * many sphere-traced views (ncw_trace_*), each with the SDF gradient and the colour network's answer, are accumulated per cell
+ * of a uniform grid in an open-addressed device table and resolved to one oriented, coloured point per occupied cell.  THE
+ * REFERENCE HAS NO SUCH TOOL: cell rule, filters and rounding below are this project's, and no parity with open3d's
+ * voxel_down_sample or any multi-view-stereo fusion is claimed.  Restated in numpy by tests/_fuse_ref.py.
+ * A sample i of the view with serial v (0 <= v <= NCW_FUSE_MAX_SERIAL): point p [3] f32 in the network's unit-sphere frame,
+ * gradient n [3] f32 (unnormalised), ray direction d [3] f32 (|d| = 1 as the ray kernels write it), colour c [3] f32.
+ * Grid (NcwFuseGrid, a HOST struct): lo [3], cell size h > 0, dims [3] each in 1 .. 2^20, the frame change x = p scale + off,
+ * cos_min and the facing switch.  ALL ARITHMETIC BELOW IS FLOAT64 (f32 inputs converted exactly), EVERY PRODUCT, SUM AND
+ * QUOTIENT ROUNDED ON ITS OWN (no fused multiply-add), divisions and square roots IEEE.
+ *  1 QUANTISE    x_a = (double)p_a scale + off_a;  g_a = (x_a - lo_a) / h;  cell_a = floor(g_a).  The sample is VALID iff
+ *                  - every p_a, n_a, d_a is finite,
+ *                  - 0 <= cell_a < dims_a on all axes,
+ *                  - nn = (n_x n_x + n_y n_y) + n_z n_z is finite and > 0,
+ *                  - facing != 0:  -((n_x d_x + n_y d_y) + n_z d_z) >= cos_min sqrt(nn)   (facing == 0: no such test).
+ *                key = (cell_z dims_y + cell_y) dims_x + cell_x (int64); an invalid sample has key -1 and adds nothing.
+ *                Payload, all integers:  qpos_a = min((int)floor((g_a - cell_a) 65536), 65535);
+ *                qn_a = llrint(n_a / sqrt(nn) * 32767) (the quotient, then the product; ties to even);
+ *                qc_a = llrint(min(max(c_a, 0), 1) * 255), a NaN colour giving 0.
+ *  2 ACCUMULATE  Per key the table holds acc [NCW_FUSE_ACC] int64 = count, sum qpos [3], sum qn [3], sum qc [3], and views
+ *                int32 = the number of DISTINCT serials that contributed.  Only integers are added: the content is a function
+ *                of the multiset of (sample, serial) pairs alone -- not of sample order, of how a view's samples are split
+ *                into calls, or of the run.  (WHERE in the table a key sits does depend on the run; nothing reads that.)
+ *  3 RESOLVE     One lane per occupied cell, cells in ascending key (the caller's row list).  With S = sum qpos, N = sum qn:
+ *                  pos_a = lo_a + ((double)cell_a + ((double)S_a / (double)count + 0.5) / 65536.0) h,
+ *                  L = sqrt((N_x N_x + N_y N_y) + N_z N_z);  L == 0: normal = 0 and degenerate = 1, else
+ *                  normal_a = (float)(N_a / L);
+ *                  colour_a = (2 sum qc_a + count) / (2 count) in integers (rule 9 of the mesh simplification).
+ *                Every position lies strictly inside its cell (the mean offset is in [0.5, 65535.5] / 65536).
+ * THE TABLE (NcwFuseTable, a HOST struct of device pointers): capacity = a power of two; keys [capacity] int64, NCW_FUSE_EMPTY
+ * in a free slot; acc [capacity, NCW_FUSE_ACC] int64; stamp, views [capacity] int32; counters [NCW_FUSE_COUNTERS] int64
+ * (occupied slots, dropped samples, valid samples).  The caller creates it with keys = EMPTY and everything else 0.
+ * Open addressing, linear probing from a 64-bit mix of the key (splitmix64's finaliser) masked to the capacity; an EMPTY word
+ * is claimed by compare-and-swap; the payload goes in by integer atomic adds; old = atomicMax(&stamp, v + 1) and views += 1 iff
+ * old < v + 1 -- correct because the caller hands out serials that NEVER DECREASE (samples of one serial may arrive in several
+ * calls).  The probe loop is bounded by the capacity: a sample that finds neither its key nor an EMPTY word adds 1 to
+ * counters[NCW_FUSE_CNT_OVERFLOW] and is dropped (the caller keeps the table at most half full and turns a non-zero counter
+ * into an error).  No lane waits for another (no spin, no lock, no flag hand-off).  While a launch inserts, every word of the
+ * table is touched only by agent-scope atomics or relaxed agent-scope atomic loads -- no plain loads or stores (the L2s of the
+ * XCDs are not coherent for those) -- and there are no float atomics.  The counters are summed per wave before one atomic.
+ *   ncw_fuse_insert  : rules 1, 2 for n samples of serial `serial` in ONE launch, one lane per sample.
+ *   ncw_fuse_move    : every occupied row of src is added into dst (capacity >= src's, different storage) by the same
+ *                      find-or-claim and atomics; dst's stamp = max, views += src's views (a key is in src once).  dst's
+ *                      occupied / overflow counters count what the move did; the valid counter is the caller's to carry.
+ *   (caller)         : rows [C] int64 = the slots with keys >= 0, sorted by their key ascending (torch.nonzero / torch.sort).
+ *   ncw_fuse_resolve : rule 3 for the C rows: pos [C,3] f64, normal [C,3] f32, colour [C,3] u8, count [C] int64, views [C]
+ *                      int32, degenerate [C] u8, keys [C] int64.  A row outside [0, capacity) or without a key of this grid
+ *                      gives zeros, degenerate 1 and key -1, and is never used as an index.
+ * All return NCW_E_BADARG without a launch for a missing or misaligned pointer (8 bytes for 64-bit words, 4 for 32-bit), n
+ * outside [0, 2^31 - 1], a serial outside [0, NCW_FUSE_MAX_SERIAL], a capacity that is not a power of two in
+ * [1, 2^NCW_FUSE_MAX_CAPACITY_LOG2], n_rows > capacity, h not finite and > 0, lo / scale / off (and cos_min when facing) not
+ * finite, or a dimension outside [1, 2^NCW_FUSE_MAX_DIM_LOG2]; 0 without a launch for an empty range.
+ * ---------------------------------------------------------------------------------------- */
+#define NCW_FUSE_ACC 10
+#define NCW_FUSE_COUNTERS 4
+#define NCW_FUSE_CNT_OCCUPIED 0
+#define NCW_FUSE_CNT_OVERFLOW 1
+#define NCW_FUSE_CNT_VALID 2
+#define NCW_FUSE_EMPTY (-1)
+#define NCW_FUSE_MAX_DIM_LOG2 20
+#define NCW_FUSE_MAX_CAPACITY_LOG2 36
+#define NCW_FUSE_MAX_SERIAL 0x7ffffffe
+typedef struct NcwFuseGrid {
+    double lo[3];
+    double h;
+    int64_t dims[3];
+    double scale;
+    double off[3];
+    double cos_min;
+    int32_t facing; /* 0: the facing test is switched off */
+    int32_t _pad;
+} NcwFuseGrid;
+typedef struct NcwFuseTable {
+    int64_t* keys;
+    int64_t* acc;
+    int32_t* stamp;
+    int32_t* views;
+    int64_t* counters;
+    int64_t capacity;
+} NcwFuseTable;
+int ncw_fuse_insert(const float* points, const float* grads, const float* dirs, const float* colours, int64_t n, int32_t serial,
+                    const NcwFuseGrid* grid, const NcwFuseTable* table, void* stream);
+int ncw_fuse_move(const NcwFuseTable* src, const NcwFuseTable* dst, void* stream);
+int ncw_fuse_resolve(const NcwFuseTable* table, const int64_t* rows, int64_t n_rows, const NcwFuseGrid* grid, double* pos,
+                     float* normal, uint8_t* colour, int64_t* count, int32_t* views, uint8_t* degenerate, int64_t* keys,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -133,17 +133,33 @@ def read_mesh(path):
     return np.ascontiguousarray(verts, dtype=np.float64), np.ascontiguousarray(faces, dtype=np.int64), cols
 
 
-def write(path, xyz, faces=None, rgb=None, coord="f8"):
+def read_normals(path):
+    """float32 [V,3] vertex normals (the vertex properties nx / ny / nz; other types are cast) of an ascii / binary PLY, vertices
+    as stored (no welding: row i belongs to row i of read_mesh's vertices); None when the file has none."""
+    for e, c in _walk(*_load(path)):
+        if e["name"] == "vertex":
+            if not all(k in c for k in ("nx", "ny", "nz")):
+                return None
+            return np.ascontiguousarray(np.stack([c[k] for k in ("nx", "ny", "nz")], -1).astype(np.float32).reshape(-1, 3))
+    return None
+
+
+def write(path, xyz, faces=None, rgb=None, coord="f8", normals=None):
     """Binary little-endian PLY of the points xyz [V,3]: `coord` = 'f8' writes double x / y / z (open3d's write_point_cloud,
-    utils/reproj_filter.py:293-300), 'f4' float (trimesh's export, tools/extract_mesh.py:160-168); rgb [V,3]: uchar red /
-    green / blue; faces [F,3] (None = a point cloud without a face element; an empty array = `element face 0`): `property
-    list uchar int vertex_indices`."""
+    utils/reproj_filter.py:293-300), 'f4' float (trimesh's export, tools/extract_mesh.py:160-168); normals [V,3]: float nx /
+    ny / nz behind the coordinates (where open3d and meshlab write them); rgb [V,3]: uchar red / green / blue; faces [F,3]
+    (None = a point cloud without a face element; an empty array = `element face 0`): `property list uchar int
+    vertex_indices`."""
     hdr = ["ply", "format binary_little_endian 1.0"]
     xyz = np.ascontiguousarray(xyz, dtype="<" + coord).reshape(-1, 3)
     hdr.append("element vertex %d" % xyz.shape[0])
     hdr += ["property %s %s" % ({"f4": "float", "f8": "double"}[coord], c) for c in "xyz"]
-    vrec = np.empty(xyz.shape[0], dtype=[("p", "<" + coord, 3)] + ([("c", "u1", 3)] if rgb is not None else []))
+    vrec = np.empty(xyz.shape[0], dtype=[("p", "<" + coord, 3)] + ([("n", "<f4", 3)] if normals is not None else [])
+                    + ([("c", "u1", 3)] if rgb is not None else []))
     vrec["p"] = xyz
+    if normals is not None:
+        hdr += ["property float nx", "property float ny", "property float nz"]
+        vrec["n"] = np.asarray(normals).reshape(-1, 3)
     if rgb is not None:
         hdr += ["property uchar red", "property uchar green", "property uchar blue"]
         vrec["c"] = np.asarray(rgb).reshape(-1, 3)

@@ -235,7 +235,7 @@ TRACE_CHUNK = 1 << 17  # rays per trace_rays call of trace_view (scripts/bench_t
 
 
 def trace_view(rdr, camera, ts, *, chunk=TRACE_CHUNK, background_rgb=None, a_code=None, gt=None, shade=True, ssim_window=3,
-               device=None, shade_prec=None, **trace_kw):
+               device=None, shade_prec=None, on_hits=None, **trace_kw):
     """The surface of one whole view by sphere tracing (trace.py; not in the reference): per chunk `ncw_view_rays` ->
     trace.trace_rays -> `NeuconW.forward([p, d, a])` over the rays that HIT (ascending ray index) -> `ncw_trace_store`.
     No background NeRF and no transmittance: a pixel shows the colour network's answer AT the first surface point, or
@@ -246,7 +246,10 @@ def trace_view(rdr, camera, ts, *, chunk=TRACE_CHUNK, background_rgb=None, a_cod
     launches); with gt also mse / psnr / ssim over the image as render_view computes them and psnr_hit over the hit pixels.
     shade=False skips the forward (colour stays background, normal 0).  shade_prec: precision of the forward (None = the
     renderer's `infer_prec` or fp32, as NeuconWRenderer.rgb); trace_kw goes to trace_rays (eps, max_iter, step, far_override,
-    sdf_fn, sync_every, prec)."""
+    sdf_fn, sync_every, prec).  on_hits(p0, hit, points, dirs, rgb, grad): called once per chunk that has a hit, after its
+    forward, with the chunk's first pixel, the chunk-local indices of the HIT rays [h] int64 (ascending) and, for those rays,
+    the surface points [h, 3] (unit-sphere frame), ray directions [h, 3], colours [h, 3] and SDF gradients [h, 3] -- the hook
+    of surfcloud.fuse_views; it needs shade=True.  The planes do not depend on it."""
     from . import trace as T
     from .neuconw import default_infer_prec
 
@@ -258,6 +261,8 @@ def trace_view(rdr, camera, ts, *, chunk=TRACE_CHUNK, background_rgb=None, a_cod
     device = torch.device(device)
     if device.type != "cuda":
         raise L.NeuconwHipError("views.trace_view: the renderer is not on a GPU; the hot path has no CPU fallback")
+    if on_hits is not None and not shade:
+        raise ValueError("trace_view: on_hits needs shade=True (it receives the colours and gradients of the forward)")
     bg = [0.0, 0.0, 0.0]
     if background_rgb is not None:
         if torch.as_tensor(background_rgb).numel() != 3:
@@ -296,6 +301,8 @@ def trace_view(rdr, camera, ts, *, chunk=TRACE_CHUNK, background_rgb=None, a_cod
                     x = torch.cat([tr["points"][hit], r[hit, 3:6], a_row.expand(h, -1)], 1).unsqueeze(1)
                     rgb, _, _, grad = rdr.neuconw(x, shade_prec)
                     forwards += 1
+                    if on_hits is not None:
+                        on_hits(p0, hit, x[:, 0, 0:3], x[:, 0, 3:6], rgb.reshape(h, 3), grad.reshape(h, 3))
                 else:
                     hit = None
             T.store_chunk(planes, p0, tr, hit, rgb, grad, bg)
