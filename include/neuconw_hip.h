@@ -726,6 +726,49 @@ int ncw_nn_query_within(const float* pts_sorted, const int32_t* cell_range, cons
 
 
 /* ------------------------------------------------------------------------------------------
+ * Exact k nearest neighbours on the grid above, and the PCA of a neighbour list (cloud normals, statistical outlier removal,
+ * normal consistency of the mesh evaluation).  The file is built without a * b + c -> fma contraction: d2 = dx*dx + dy*dy +
+ * dz*dz with dx = P[i].x - q.x rounds every operation, and so does every float64 operation of ncw_knn_pca.
+ *   ncw_knn_query: the tables of a built grid (pts_sorted, cell_range, the coarse level of ncw_nn_coarse and its B), the
+ *                  queries q [n,3] f32 and q_order as ncw_nn_query_within.  With r2 = max_dist * max_dist (one float32 product,
+ *                  formed by this entry) the admitted set of query j is {(d2(q_j, P[i]), i) : d2 <= r2 (inclusive), i !=
+ *                  exclude[j]}; row j gets its k smallest elements under the LEXICOGRAPHIC order (d2, i) -- a tie on d2 goes to the
+ *                  smaller index, as in the 1-NN kernels -- in ascending order: idx [n,k] int32, dist [n,k] f32 = sqrtf(d2),
+ *                  count [n] int32 = the number of entries; ranks beyond count hold -1 / +inf.  max_dist = +inf: no bound.
+ *                  exclude [n] int32 or NULL: an index into P, or -1; that index alone is never reported for query j (a cloud
+ *                  querying itself); a duplicate of that point at d = 0 stays.  A query with a NaN or infinite coordinate
+ *                  gets count = 0.  1 <= k <= 32; fewer than k admitted points give a short row.
+ *                  The walk is ncw_nn_query_within's with min(best d2, r2) replaced by min(kth, r2), kth = the current k-th best
+ *                  d2 (+inf while the list is short), every comparison strict as there; each cell is scanned at most once (the
+ *                  coarse phase skips the fine cells already walked), so no index repeats in a row.  One launch, no escape
+ *                  list, no brute-force pass, no atomics: the outputs are a function of the inputs only, bitwise reproducible
+ *                  and the same for any split of the queries into launches.  The candidate list is k x wg (d2, index) pairs
+ *                  of LDS; wg = the workgroup size, 64, 128 or 256 (0 = the default, 64).  work [n,2] int32 or NULL: per
+ *                  query the distance evaluations and the list insertions (measurement only).
+ *                  NCW_E_BADARG without a launch for a NULL pointer (exclude and work excepted), a bad grid, B not a power of two
+ *                  in [1, 65536], margin < 0 or NaN, max_dist <= 0 or NaN, k outside [1, 32], another wg; 0 without a
+ *                  launch for n <= 0.
+ *   ncw_knn_pca  : per point j of pts [n,3] f32 its members: the point itself first when with_query, then
+ *                  ref[idx[j, r]] [m,3] f32 for r < count[j] in list order (a list ends at an index outside [0, m)).  In
+ *                  float64, every operation rounded once: the mean (sum in member order, / n_j), the six covariance sums of
+ *                  (a - mean_a)(b - mean_b) in member order, / n_j; cyclic Jacobi, 8 sweeps of the rotations (0,1), (0,2),
+ *                  (1,2), a rotation skipped where its off-diagonal is exactly 0 (theta = (aqq - app) / (2 apq), t = sign(theta)
+ *                  / (|theta| + sqrt(theta^2 + 1)), c = 1 / sqrt(t^2 + 1), s = t c); eigenvalues sorted ascending by the
+ *                  compare-swaps (0,1), (1,2), (0,1).  eig [n,3] f64 ascending; curvature [n] f32 = l0 / (l0 + l1 + l2), 0
+ *                  when the sum is 0; valid [n] uint8 = n_j >= 3 and l1 > 1e-10 l2 (collinear or coincident members have
+ *                  no normal); normal [n,3] f32 = the eigenvector of l0 divided by its length, 0 where invalid.  Sign: with
+ *                  toward (a HOST pointer to 3 floats, read by this entry; NULL = none) flipped so that n . (toward - p) >= 0 in
+ *                  float64; otherwise so that its component of largest magnitude (the first such on ties) is positive.
+ *                  n_j = 0 gives zeros.  NCW_E_BADARG for a NULL pointer (toward excepted) or k outside [1, 32].
+ * ---------------------------------------------------------------------------------------- */
+int ncw_knn_query(const float* pts_sorted, const int32_t* cell_range, const int32_t* coarse, int B, const float* q,
+                  const int64_t* q_order, const int32_t* exclude, int64_t n, const NcwNnGrid* grid, float margin, float max_dist,
+                  int k, int wg, int32_t* idx, float* dist, int32_t* count, int32_t* work, void* stream);
+int ncw_knn_pca(const float* pts, const float* ref, int64_t m, const int32_t* idx, const int32_t* count, int64_t n, int k,
+                int with_query, const float* toward, float* normal, double* eig, float* curvature, uint8_t* valid, void* stream);
+
+
+/* ------------------------------------------------------------------------------------------
  * Triangle depth rasterizer of the reprojection visibility filter: replaces the pyrender depth render of
  * utils/pyrender_renderer.py:16-24 (utils/reproj_filter.py:208), the back-projection `reproject` of
  * utils/reproj_filter.py:133-152 and the per-pixel open3d KD-tree marking loop of :229-232 (with ncw_nn_*).

@@ -205,6 +205,58 @@ class NNGrid:
             stats["beyond"] = stats.get("beyond", 0) + (int((idx < 0).sum()) if n else 0)
         return dist, idx
 
+    def query_k(self, q32, k, max_dist=None, exclude=None, stats=None, wg=0):
+        """(dist [N,k] f32, idx [N,k] int32, count [N] int32): every query's k nearest points of P (`ncw_knn_query`): the k
+        smallest (d^2, index) pairs in lexicographic order -- a tie on d^2 goes to the smaller index -- ascending; with
+        `max_dist` only points with d^2 <= float32(max_dist)^2 (inclusive); rows beyond `count` hold +inf / -1.  `exclude`
+        [N] int32 (or None): an index into P, or -1, that is never reported for that query (a cloud querying itself: only
+        that index, a duplicate of the point stays).  A NaN or infinite query gets count 0.  One launch over the coarse level
+        (built on the first call, as `query_within`): exact, no brute-force pass.  stats (dict) gets `evals` and `inserts`
+        (distance evaluations and list insertions, summed over the queries).  `wg`: the workgroup size (0 = the default).
+        ValueError unless 1 <= k <= 32 and max_dist > 0."""
+        _check_k("evalmesh.NNGrid.query_k", k, max_dist)
+        if not q32.is_cuda or (exclude is not None and not exclude.is_cuda):
+            raise L.NeuconwHipError("evalmesh.NNGrid.query_k: the queries are not on a GPU; there is no CPU fallback")
+        lib = L.get_lib()
+        if self.coarse is None:
+            self.build_coarse()
+        k = int(k)
+        n = int(q32.shape[0])
+        q32 = q32.contiguous()
+        dist = torch.empty(n, k, dtype=torch.float32, device=self.dev)
+        idx = torch.empty(n, k, dtype=torch.int32, device=self.dev)
+        count = torch.empty(n, dtype=torch.int32, device=self.dev)
+        work = torch.empty(n, 2, dtype=torch.int32, device=self.dev) if stats is not None else None
+        if exclude is not None:
+            exclude = exclude.to(torch.int32).contiguous()
+            if exclude.shape != (n,):
+                raise ValueError("evalmesh.NNGrid.query_k: exclude must have one entry per query")
+        if n:
+            keys = torch.empty(n, dtype=torch.int32, device=self.dev)
+            s = L.stream_ptr(self.dev)
+            L.check(lib.ncw_nn_cell_keys(L.ptr(q32), n, C.byref(self.cgrid), L.ptr(keys), s), "ncw_nn_cell_keys")
+            q_order = torch.sort(keys, stable=True)[1].contiguous()
+            L.check(lib.ncw_knn_query(L.ptr(self.pts), L.ptr(self.range), L.ptr(self.coarse), self.coarse_block, L.ptr(q32),
+                                      L.ptr(q_order), L.ptr(exclude) if exclude is not None else None, n, C.byref(self.cgrid),
+                                      float(self.margin), float("inf") if max_dist is None else float(max_dist), k, int(wg),
+                                      L.ptr(idx), L.ptr(dist), L.ptr(count), L.ptr(work) if work is not None else None, s),
+                    "ncw_knn_query")
+        if stats is not None:
+            tot = work.long().sum(0).tolist() if n else [0, 0]
+            stats["evals"] = stats.get("evals", 0) + int(tot[0])
+            stats["inserts"] = stats.get("inserts", 0) + int(tot[1])
+        return dist, idx, count
+
+
+KNN_MAX_K = 32
+
+
+def _check_k(what, k, max_dist):
+    if not (isinstance(k, (int, np.integer)) and 1 <= int(k) <= KNN_MAX_K):
+        raise ValueError("%s: k must be an integer in [1, %d], got %r" % (what, KNN_MAX_K, k))
+    if max_dist is not None and not float(max_dist) > 0:
+        raise ValueError("%s: max_dist must be > 0, got %r" % (what, max_dist))
+
 
 def recentre(ref, query):
     """Both clouds moved to their common box centre in float64, then cast to f32 (scene coordinates are metres and may be
@@ -244,6 +296,32 @@ def nn_distances(ref, query, max_shell=MAX_SHELL, stats=None, max_dist=None):
     if max_dist is not None:
         return grid.query_within(q32, max_dist, stats)
     return grid.query(q32, stats)
+
+
+@torch.no_grad()
+def knn(ref, query, k, max_dist=None, exclude_self=False, stats=None):
+    """For every query point its k nearest points of `ref`: (dist [N,k] float32, idx [N,k] int32, count [N] int32), exact,
+    ascending, ties on equal d^2 to the smaller index, rows beyond `count` +inf / -1 (`NNGrid.query_k`; the clouds are
+    recentred as in `nn_distances`).  max_dist: only points within it (inclusive).  exclude_self: `query` is `ref` itself
+    (the same number of points) and point i is never its own neighbour (a duplicate of it is).  Empty results when either
+    side is empty.  ValueError unless 1 <= k <= 32 and max_dist > 0; NeuconwHipError for CPU tensors."""
+    _check_k("evalmesh.knn", k, max_dist)
+    if not (ref.is_cuda and query.is_cuda):
+        raise L.NeuconwHipError("evalmesh.knn: the clouds are not on a GPU; there is no CPU fallback")
+    dev = ref.device
+    ref, query = ref.reshape(-1, 3), query.reshape(-1, 3)
+    n, k = int(query.shape[0]), int(k)
+    if exclude_self and ref.shape[0] != n:
+        raise ValueError("evalmesh.knn: exclude_self needs query to be ref itself (%d != %d points)" % (n, ref.shape[0]))
+    if ref.shape[0] == 0 or n == 0:
+        return (torch.full((n, k), float("inf"), dtype=torch.float32, device=dev),
+                torch.full((n, k), -1, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev))
+    r32, q32, cmax, _ = recentre(ref, query)
+    grid = NNGrid(r32, cmax)
+    if stats is not None:
+        stats.update(dims=list(grid.dims), cells=grid.ncells, refined=grid.refined)
+    exclude = torch.arange(n, dtype=torch.int32, device=dev) if exclude_self else None
+    return grid.query_k(q32, k, max_dist=max_dist, exclude=exclude, stats=stats)
 
 
 # ---------------------------------------------------------------------------------------------------
@@ -754,7 +832,7 @@ def _write_points(path, pts):
 
 def eval_mesh(file_pred, file_trgt, scene_config, is_mesh, threshold=.1, bbx_name="eval_bbx", save_name="eval", sfm=None,
               device=None, verbose=True, surface=None, surface_seed=0, surface_mode="stratified", error_clouds=None,
-              exact_recall=False):
+              exact_recall=False, normals=None):
     """utils/eval_mesh.py:48-123 with use_o3d=False: load both PLYs (ply.read_points; `is_mesh` is accepted and, as in the
     reference's trimesh branch, not used), carry the prediction to GT coordinates by scene_config['sfm2gt'], crop both to
     scene_config[bbx_name], optionally crop both to the voxels of the filtered SfM points, nearest neighbours in both
@@ -782,7 +860,23 @@ def eval_mesh(file_pred, file_trgt, scene_config, is_mesh, threshold=.1, bbx_nam
     The precision side is unchanged (samples with `surface=k`, vertices otherwise).  One difference from the sampled path
     under the SfM crop: the GT queries are cropped to the SfM voxels as always, the triangles are NOT clipped to them (a
     triangle is not a point: it may cross voxels), so a GT point may be matched to surface that the sampled path would have
-    cropped away.  metrics.json then carries "recal_mode": "exact"; with the option off every written byte is as before."""
+    cropped away.  metrics.json then carries "recal_mode": "exact"; with the option off every written byte is as before.
+
+    `normals` = K (an integer in [1, 32]; default None) adds the NORMAL CONSISTENCY of the two scored clouds: after all
+    crops the normals of the scored prediction points and of the scored GT points are estimated, each from its own K
+    nearest neighbours (`cloudops.estimate_normals`; unoriented), and over the nearest-neighbour pairs the distances
+    already use the mean of |n_a . n_b| is formed in float64 where both normals are valid.  The summary metrics.json gets
+    `normal_consistency_pred2gt` (every predicted point with its nearest GT point), `normal_consistency_gt2pred`, their mean
+    `normal_consistency`, `normals_k`, and per threshold the lists `normal_consistencies_pred2gt` / `_gt2pred` /
+    `normal_consistencies`: the same means over the pairs closer than the threshold (strictly, as `prec` / `recal`).  The
+    returned dict carries the three overall values too.  Refused together with `exact_recall` (ValueError, before anything
+    is written): there the GT side is paired with a triangle, not with a point that has an estimated normal.  With
+    normals=None every written byte is as before."""
+    if normals is not None:
+        _check_k("evalmesh.eval_mesh(normals=)", normals, None)
+        if exact_recall:
+            raise ValueError("evalmesh.eval_mesh: normals= and exact_recall=True cannot be combined (the exact recall pairs "
+                             "a GT point with a triangle, not with a point of the scored cloud)")
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     save_dir = os.path.join(os.path.dirname(file_pred), "eval_" + str(save_name))
     os.makedirs(save_dir, exist_ok=True)
@@ -830,8 +924,8 @@ def eval_mesh(file_pred, file_trgt, scene_config, is_mesh, threshold=.1, bbx_nam
     if exact_recall:  # for every GT point the predicted surface itself
         dist1 = mesh_distances(apply_transform(m_verts, sfm_to_gt), m_faces, g, box=scene_config[bbx_name])[0]
     else:
-        dist1, _ = nn_distances(p, g)  # for every GT point its nearest prediction (eval_mesh.py:88)
-    dist2, _ = nn_distances(g, p)  # for every predicted point its nearest GT point (:89)
+        dist1, idx1 = nn_distances(p, g)  # for every GT point its nearest prediction (eval_mesh.py:88)
+    dist2, idx2 = nn_distances(g, p)  # for every predicted point its nearest GT point (:89)
 
     thresholds = list(threshold) if isinstance(threshold, (list, tuple, np.ndarray)) else [threshold]
     all_m = metrics(dist1, dist2, thresholds)
@@ -853,12 +947,44 @@ def eval_mesh(file_pred, file_trgt, scene_config, is_mesh, threshold=.1, bbx_nam
     summary = {"thresholds": [float(t) for t in thresholds], "fscores": fscores, "precs": precs, "recals": recals}
     if exact_recall:
         summary["recal_mode"] = "exact"
+    nc = None
+    if normals is not None:
+        nc = _normal_consistency(p, g, dist1, idx1, dist2, idx2, int(normals), thresholds)
+        summary.update(nc)
     with open(os.path.join(save_dir, "metrics.json"), "w") as fh:
         json.dump(summary, fh)
     log("fscores: %s" % fscores)
     log("precs: %s" % precs)
     log("recals: %s" % recals)
+    if nc is not None:
+        log("normal consistency (k = %d): %s" % (nc["normals_k"], nc["normal_consistency"]))
+        return dict(all_m[-1], **{key: nc[key] for key in ("normal_consistency", "normal_consistency_pred2gt",
+                                                           "normal_consistency_gt2pred")})
     return all_m[-1]
+
+
+def _normal_consistency(p, g, dist1, idx1, dist2, idx2, k, thresholds):
+    """The normal-consistency keys of eval_mesh's summary: p / g the scored prediction / GT points, (dist1, idx1) for every
+    GT point its nearest prediction, (dist2, idx2) for every predicted point its nearest GT point."""
+    from . import cloudops
+
+    def half(a, b):
+        return (a + b) / 2.0
+
+    n_p, _, v_p = cloudops.estimate_normals(p, k=k)
+    n_g, _, v_g = cloudops.estimate_normals(g, k=k)
+    p2g = cloudops.normal_consistency(n_p, v_p, n_g, v_g, idx2)[0]
+    g2p = cloudops.normal_consistency(n_g, v_g, n_p, v_p, idx1)[0]
+    out = {"normal_consistency_pred2gt": p2g, "normal_consistency_gt2pred": g2p, "normal_consistency": half(p2g, g2p),
+           "normals_k": int(k), "normal_consistencies_pred2gt": [], "normal_consistencies_gt2pred": [],
+           "normal_consistencies": []}
+    for t in thresholds:
+        a = cloudops.normal_consistency(n_p, v_p, n_g, v_g, torch.where(dist2.double() < float(t), idx2, -1))[0]
+        b = cloudops.normal_consistency(n_g, v_g, n_p, v_p, torch.where(dist1.double() < float(t), idx1, -1))[0]
+        out["normal_consistencies_pred2gt"].append(a)
+        out["normal_consistencies_gt2pred"].append(b)
+        out["normal_consistencies"].append(half(a, b))
+    return out
 
 
 def parse_thresholds(text):

@@ -533,7 +533,7 @@ SCENES = {
 
 def eval_pipeline(scene_name, pred_dir, data_root="data/heritage-recon", verbose=True, surface=None, surface_seed=0,
                   surface_mode="stratified", error_clouds=None, keep_faces=False, min_corners=1, min_component_faces=0,
-                  exact_recall=False):
+                  exact_recall=False, normals=None):
     """scripts/eval_pipeline.sh in one process: the reprojection filter of <pred_dir>/mesh/extracted_mesh_level_10_colored.ply
     against itself (written to <pred_dir>/mesh/reprojected.ply), then evalmesh.eval_mesh of that file against
     <data_root>/<scene>/<scene>.ply with the scene's thresholds and the SfM crop of <data_root>/<scene>/neuralsfm, results in
@@ -542,7 +542,8 @@ def eval_pipeline(scene_name, pred_dir, data_root="data/heritage-recon", verbose
     keep_faces (default off; not in the reference): filter with reproj_filter(keep_faces=True, min_corners,
     min_component_faces) and score <pred_dir>/mesh/reprojected_mesh.ply instead, results in eval_<scene>_reprojected_mesh.ply/;
     `surface` and `exact_recall` then go to eval_mesh and work, because that file has faces.  Without keep_faces
-    exact_recall is refused (ValueError): reprojected.ply is a point cloud."""
+    exact_recall is refused (ValueError): reprojected.ply is a point cloud.  `normals` = K goes to eval_mesh (normal
+    consistency of the scored clouds)."""
     if scene_name not in SCENES:
         raise ValueError("Not supported scene: %s (one of %s)" % (scene_name, ", ".join(sorted(SCENES))))
     if exact_recall and not keep_faces:
@@ -565,4 +566,4 @@ def eval_pipeline(scene_name, pred_dir, data_root="data/heritage-recon", verbose
                               scene_config, False, threshold=evalmesh.parse_thresholds(sc["thresholds"]), bbx_name="eval_bbx",
                               save_name=scene_name + "_" + scored, sfm=sfm, verbose=verbose, surface=surface,
                               surface_seed=surface_seed, surface_mode=surface_mode, error_clouds=error_clouds,
-                              exact_recall=exact_recall)
+                              exact_recall=exact_recall, **({} if normals is None else {"normals": normals}))

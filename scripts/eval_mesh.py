@@ -16,6 +16,9 @@ ground-truth cloud, nearest neighbours on the GPU (neuralrecon_w_amd.evalmesh).
   * --exact_recall measures the recall side (GT point -> prediction) to the predicted SURFACE: exact point-to-triangle
     distances on the GPU instead of the distance to the nearest vertex or sample; the prediction must have faces; the
     precision side is unchanged; metrics.json gains "recal_mode": "exact";
+  * --normal_consistency [K] (K = 16 when omitted) adds the normal consistency of the two scored clouds to metrics.json:
+    normals of both estimated from K nearest neighbours on the GPU, |n . n'| averaged over the nearest-neighbour pairs in
+    both directions, overall and per threshold; refused with --exact_recall;
   * --error_clouds also writes visualize/<t>/error_pred_precision.ply and error_gt_recal.ply (jet colours of the errors).
 """
 import argparse
@@ -50,6 +53,8 @@ def get_opts(argv=None):
                     help="write the error-coloured clouds of every threshold")
     ap.add_argument("--exact_recall", default=False, action="store_true",
                     help="recall from exact point-to-triangle distances to the predicted mesh (needs faces)")
+    ap.add_argument("--normal_consistency", type=int, nargs="?", const=16, default=None, metavar="K",
+                    help="also report the normal consistency, normals from K nearest neighbours (K = 16 when omitted)")
     return ap.parse_args(argv)
 
 
@@ -69,7 +74,8 @@ def main(argv=None):
     evalmesh.eval_mesh(args.file_pred, args.file_trgt, scene_config, args.mesh, threshold=thresholds, bbx_name=args.bbx_name,
                        save_name=args.save_name, sfm=sfm, surface=args.sample_surface, surface_seed=args.surface_seed,
                        surface_mode=args.surface_mode, error_clouds=True if args.error_clouds else None,
-                       exact_recall=args.exact_recall)
+                       exact_recall=args.exact_recall,
+                       **({} if args.normal_consistency is None else {"normals": args.normal_consistency}))
 
 
 if __name__ == "__main__":

@@ -10,7 +10,7 @@ Reads <pred_dir>/mesh/extracted_mesh_level_10_colored.ply, <data_root>/<scene>/{
 <pred_dir>/mesh/eval_<scene>_reprojected.ply/.  As in the reference, eval_mesh applies sfm2gt to the filtered cloud that is
 already in GT coordinates: the two steps chain correctly only when sfm2gt is the identity.
 
---sample_surface / --surface_seed / --surface_mode / --error_clouds are handed to eval_mesh as scripts/eval_mesh.py does.
+--sample_surface / --surface_seed / --surface_mode / --error_clouds / --normal_consistency are handed to eval_mesh as scripts/eval_mesh.py does.
 The file the pipeline scores, reprojected.ply, is a point cloud: --sample_surface needs faces and is refused on it, and so
 is --exact_recall (exact point-to-triangle recall, scripts/eval_mesh.py), before any work: the reprojection filter does not
 keep the faces.
@@ -41,6 +41,8 @@ def parse_args(argv=None):
     ap.add_argument("--exact_recall", default=False, action="store_true",
                     help="needs --keep_faces; refused without: reprojected.ply has no faces (or score a mesh with "
                          "scripts/eval_mesh.py --exact_recall)")
+    ap.add_argument("--normal_consistency", type=int, nargs="?", const=16, default=None, metavar="K",
+                    help="also report the normal consistency, normals from K nearest neighbours (scripts/eval_mesh.py)")
     ap.add_argument("--keep_faces", default=False, action="store_true",
                     help="keep the faces through the filter and score reprojected_mesh.ply")
     ap.add_argument("--min_corners", type=int, choices=[1, 2, 3], default=1, help="--keep_faces: marked corners a face needs")
@@ -60,7 +62,8 @@ def main(argv=None):
                          surface_seed=args.surface_seed, surface_mode=args.surface_mode,
                          error_clouds=True if args.error_clouds else None, keep_faces=args.keep_faces,
                          min_corners=args.min_corners, min_component_faces=args.min_component_faces,
-                         exact_recall=args.exact_recall)
+                         exact_recall=args.exact_recall,
+                         **({} if args.normal_consistency is None else {"normals": args.normal_consistency}))
 
 
 if __name__ == "__main__":
