@@ -340,7 +340,10 @@ class LossScale:
         self.init, self.buf = float(init), None
 
     def tensor(self, device):
-        if self.buf is None or self.buf.device != torch.device(device):
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:  # "cuda" is the current device: the SAME buffer as under its indexed name
+            device = torch.device("cuda", torch.cuda.current_device())  # (the optimiser and captured graphs hold the buffer's address)
+        if self.buf is None or self.buf.device != device:
             self.buf = torch.tensor([self.init, 1.0 / self.init], device=device, dtype=torch.float32)
         return self.buf
 
@@ -476,7 +479,7 @@ class NeuconWRenderer:
                 z_new = rayops.upsample(rays_o, rays_d, z, sdf, self.n_importance // self.up_sample_steps,
                                         64 * 2 ** (self.s_val_base + i))
                 z, sdf = self.cat_z_vals(rays_o, rays_d, z, z_new, sdf, last=(i + 1 == self.up_sample_steps))
-            n_samples = self.n_samples + self.n_importance
+            n_samples = z.shape[1]  # n_samples + up_sample_steps * (n_importance // up_sample_steps)
         if self.fine_octree_data is not None and self.boundary_samples and self.boundary_samples > 0:
             zb = rayops.boundary(near, far, z, self.boundary_samples)
             z, _ = rayops.sort_merge(zb, z)
