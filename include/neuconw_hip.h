@@ -1523,6 +1523,84 @@ int ncw_fuse_resolve(const NcwFuseTable* table, const int64_t* rows, int64_t n_r
                      float* normal, uint8_t* colour, int64_t* count, int32_t* views, uint8_t* degenerate, int64_t* keys,
                      void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Synthetic scenes with known ground truth (csrc/ncw_synth.hip; neuralrecon-w_amd/synth.py).  Replaces nothing in the reference:
+ * it has no scene generator, its scenes are downloaded.  These two launches make, from a triangle mesh, what a photo collection
+ * and its SfM model give the pipeline: the image with its semantic map, and the key-point observations of one view.  Both run one
+ * lane per output element, without atomics, LDS or transcendental functions; every product, sum and quotient is rounded once
+ * (IEEE, no fused multiply-add), so tests/_synth_ref.py restates them in numpy bit for bit.  What needs a square root is handed in
+ * by the host (unit face normals, sigma sqrt(3)).
+ *
+ *   ncw_synth_shade   : deferred shading of ONE image from the depth / face planes ncw_raster_resolve wrote at ss x ss samples
+ *                       per pixel (depth_ss, face_ss: [height ss][width ss], ss in 1..NCW_SYNTH_MAX_SS).
+ *       Pixel convention: the project's rays go through INTEGER pixel coordinates (ncw_view_rays: dir = ((c - cx) / fx, ..)),
+ *       the rasterizer samples at (c + 0.5, r + 0.5).  The image written here is the one those rays see: sub-sample (i, j) of
+ *       pixel (r, c) sits at image point (c + (i + 0.5) / ss - 0.5, r + (j + 0.5) / ss - 0.5), and the caller rasterizes the
+ *       (height ss) x (width ss) planes with fx ss, fy ss, cx ss + 0.5 ss, cy ss + 0.5 ss.  img->fx .. cy are those of the
+ *       height x width image itself.
+ *       Per sub-sample with a face f in [0, n_faces): camera point (x d, y d, d) with x = (px - cx) / fx, y = (py - cy) / fy
+ *       (OpenCV axes) -> world through c2w -> GT frame through sfm2gt (both row-major 3x4, float32, a b + c d + e f + g left to
+ *       right).  albedo[c] = base[c] (1 + amp (n - 0.4375)), n = n0 / 2 + n1 / 4 + n2 / 8, n_o = value noise of the GT point
+ *       times freq 2^o: the lattice value at integer (ix, iy, iz) is (w >> 8) 2^-24 with w = word 0 of Philox4x32-10 of counter
+ *       (ix, iy, iz, tex_seed) and key (o, 0), interpolated trilinearly (x, then y, then z) as a + t (b - a); lattice
+ *       coordinates are clamped to +-2^30.  Flat Lambert: s = ambient + diffuse max(0, normal[f] . light) (normal: unit, the
+ *       caller's frame; light: unit, the same frame).  v[c] = clamp(gain[c] albedo[c] s + bias[c], 0, 1).  A sub-sample without a
+ *       face (face < 0 or >= n_faces, or depth <= 0) takes sky_top + t (sky_bottom - sky_top), t = r / height, clamped likewise.
+ *       rgb[r][c][ch] = uint8(mean 255 + 0.5) by truncation, the mean taken in (j, i) order and divided by ss ss; label[r][c] and
+ *       depth[r][c] are those of sub-sample (ss / 2, ss / 2): the material's label (sky_label without a face), the depth (0).
+ *       materials[n_materials] on the device, indexed by face_material[f] (uint8, clamped to n_materials - 1); 1 <= n_materials
+ *       <= 256.  height width ss ss < 2^31.
+ *   ncw_synth_observe : key-point observations of ONE view of n points (pts, nrm: float64 [n][3], world frame, nrm unit; index:
+ *       int64 [n], the point's identity).  (x, y, z) = w2c p (row-major 3x4 float64); in front when z > znear; u = fx (x / z) + cx,
+ *       v = fy (y / z) + cy; facing when nrm . (centre - p) > 0; the observed pixel (floor(u + 0.5), floor(v + 0.5)) of the
+ *       NOISE-FREE projection must lie in the image; visible when depth[row][col] > 0 and |z - depth| <= depth_tol z (depth: the
+ *       float32 [height][width] plane ncw_synth_shade wrote, occluders included).  Noise per axis: sigma_r3 (u1 + u2 + u3 + u4 - 2),
+ *       sigma_r3 = sigma sqrt(3) from the host: mean 0, variance sigma^2, |noise| <= 2 sqrt(3) sigma.  u_k = (w >> 8) 2^-24 of
+ *       the words of Philox4x32-10 with key (seed, seed >> 32) and counters (index, index >> 32, serial, 0) for x and
+ *       (.., 1) for y: a draw depends on the point's index and the view's serial alone, never on n or the launch.
+ *       xy[n][2] = (u, v) + noise, err2[n] = the SQUARED pixel distance of the noisy from the true projection (the caller takes
+ *       the root), vis[n] = 1 / 0.  A point with z <= znear writes xy = 0, err2 = 0, vis = 0.
+ * Return codes: 0; NCW_E_BADARG for a NULL pointer, ss outside 1..NCW_SYNTH_MAX_SS, an empty or too large image, n_materials
+ * outside 1..256, non-positive fx / fy / znear, negative sigma_r3 / depth_tol; n <= 0 (observe) returns 0 at once.
+ * ---------------------------------------------------------------------------------------- */
+#define NCW_SYNTH_MAX_SS 4
+typedef struct NcwSynthMaterial {
+    float base[3];  /* base colour, linear [0, 1] */
+    float freq;     /* lattice cells per GT unit of the first octave */
+    float amp;      /* texture amplitude */
+    int32_t label;  /* ADE20K label id written to the label plane (0..255) */
+} NcwSynthMaterial;
+typedef struct NcwSynthImage {
+    float fx, fy, cx, cy;
+    float c2w[12];
+    float sfm2gt[12];
+    float light[3];
+    float ambient, diffuse;
+    float gain[3], bias[3];
+    float sky_top[3], sky_bottom[3];
+    int32_t height, width, ss;
+    int32_t sky_label;
+    uint32_t tex_seed;
+    int32_t _pad;
+} NcwSynthImage;
+typedef struct NcwSynthView {
+    double w2c[12];
+    double centre[3];
+    double fx, fy, cx, cy;
+    double znear;
+    double sigma_r3;
+    double depth_tol;
+    uint64_t seed;
+    int32_t height, width;
+    uint32_t serial;
+    int32_t _pad;
+} NcwSynthView;
+int ncw_synth_shade(const float* depth_ss, const int32_t* face_ss, const NcwSynthImage* img, const float* face_normal,
+                    const uint8_t* face_material, int64_t n_faces, const NcwSynthMaterial* materials, int32_t n_materials,
+                    uint8_t* rgb, uint8_t* label, float* depth, void* stream);
+int ncw_synth_observe(const double* pts, const double* nrm, const int64_t* index, int64_t n, const NcwSynthView* view,
+                      const float* depth, double* xy, double* err2, uint8_t* vis, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

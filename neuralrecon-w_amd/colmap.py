@@ -105,6 +105,91 @@ def read_points3d(path, with_tracks=False):
     return ids, xyz, err, track, start, np.ascontiguousarray(flat[:, 0]), np.ascontiguousarray(flat[:, 1])
 
 
+# ---------------------------------------------------------------------------------------------------
+# writers: exactly the layouts the three readers document (synth.py writes its scenes with them)
+# ---------------------------------------------------------------------------------------------------
+def write_cameras(path, cams):
+    """cameras.bin from {camera_id: dict(model, width, height, params)} or an iterable of such dicts carrying `id`, in the order
+    given.  Only PINHOLE (model id 1, four parameters fx, fy, cx, cy) is written: anything else is a ValueError."""
+    items = [(int(k), c) for k, c in cams.items()] if isinstance(cams, dict) else [(int(c["id"]), c) for c in cams]
+    out = [struct.pack("<Q", len(items))]
+    for cid, c in items:
+        params = np.asarray(c["params"], dtype=np.float64).reshape(-1)
+        if int(c.get("model", PINHOLE)) != PINHOLE or params.size != 4:
+            raise ValueError("write_cameras: camera %d is not PINHOLE (model id %r, %d parameters)"
+                             % (cid, c.get("model", PINHOLE), params.size))
+        out.append(struct.pack("<iiQQ", cid, PINHOLE, int(c["width"]), int(c["height"])) + params.astype("<f8").tobytes())
+    with open(path, "wb") as fh:
+        fh.write(b"".join(out))
+
+
+def write_images(path, images):
+    """images.bin from {image_id: dict(qvec, tvec, camera_id, name[, xys, point3d_ids])} or an iterable of such dicts carrying
+    `id`, in the order given.  Without `xys` an image has no 2-D point.  A name that holds NUL (the terminator of the name
+    field) and xys / point3d_ids of different lengths are ValueErrors."""
+    items = [(int(k), im) for k, im in images.items()] if isinstance(images, dict) else [(int(im["id"]), im) for im in images]
+    pt = np.dtype([("x", "<f8"), ("y", "<f8"), ("id", "<i8")])
+    out = [struct.pack("<Q", len(items))]
+    for iid, im in items:
+        name = str(im["name"]).encode("utf-8")
+        if b"\x00" in name:
+            raise ValueError("write_images: the name of image %d holds NUL, which ends the name field" % iid)
+        xys = np.asarray(im.get("xys", np.empty((0, 2))), dtype=np.float64).reshape(-1, 2)
+        ids = np.asarray(im.get("point3d_ids", np.full(len(xys), -1)), dtype=np.int64).reshape(-1)
+        if len(ids) != len(xys):
+            raise ValueError("write_images: image %d has %d 2-D points and %d point3D ids" % (iid, len(xys), len(ids)))
+        q, t = np.asarray(im["qvec"], dtype=np.float64).reshape(4), np.asarray(im["tvec"], dtype=np.float64).reshape(3)
+        rec = np.empty(len(xys), dtype=pt)
+        rec["x"], rec["y"], rec["id"] = xys[:, 0], xys[:, 1], ids
+        out.append(struct.pack("<i7di", iid, *q, *t, int(im["camera_id"])) + name + b"\x00" + struct.pack("<Q", len(xys))
+                   + rec.tobytes())
+    with open(path, "wb") as fh:
+        fh.write(b"".join(out))
+
+
+def write_points3d(path, ids, xyz, rgb, err, track_start, track_image_id, track_point2d_idx):
+    """points3D.bin from the arrays `read_points3d(.., with_tracks=True)` returns plus the colours: ids [N], xyz [N, 3], rgb uint8
+    [N, 3], err [N], and the tracks as CSR arrays (track_start [N + 1], track_image_id [T], track_point2d_idx [T]).  Arrays whose
+    lengths disagree (N, or T against track_start[-1]) are a ValueError."""
+    ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+    n = len(ids)
+    xyz = np.asarray(xyz, dtype=np.float64).reshape(-1, 3)
+    rgb = np.asarray(rgb, dtype=np.uint8).reshape(-1, 3)
+    err = np.asarray(err, dtype=np.float64).reshape(-1)
+    start = np.asarray(track_start, dtype=np.int64).reshape(-1)
+    t_img = np.asarray(track_image_id, dtype=np.int32).reshape(-1)
+    t_idx = np.asarray(track_point2d_idx, dtype=np.int32).reshape(-1)
+    if not (len(xyz) == len(rgb) == len(err) == n and len(start) == n + 1):
+        raise ValueError("write_points3d: %d ids, %d xyz, %d rgb, %d err, %d track_start (N + 1 expected)"
+                         % (n, len(xyz), len(rgb), len(err), len(start)))
+    if len(t_img) != len(t_idx) or int(start[0]) != 0 or int(start[-1]) != len(t_img) or (np.diff(start) < 0).any():
+        raise ValueError("write_points3d: %d track image ids, %d 2-D point indices, track_start runs %d .. %d"
+                         % (len(t_img), len(t_idx), int(start[0]), int(start[-1])))
+    elems = np.stack([t_img, t_idx], -1).astype("<i4")
+    out = [struct.pack("<Q", n)]
+    for i in range(n):
+        a, b = int(start[i]), int(start[i + 1])
+        out.append(struct.pack("<QdddBBBdQ", int(ids[i]), *xyz[i], *rgb[i], err[i], b - a) + elems[a:b].tobytes())
+    with open(path, "wb") as fh:
+        fh.write(b"".join(out))
+
+
+def rotmat2qvec(R):
+    """The unit quaternion (w, x, y, z), w >= 0, of a rotation matrix: the inverse of `qvec2rotmat` (the largest of the four
+    candidate divisors, so that no case divides by a small number)."""
+    R = np.asarray(R, dtype=np.float64)
+    t = np.array([1 + R[0, 0] + R[1, 1] + R[2, 2], 1 + R[0, 0] - R[1, 1] - R[2, 2], 1 - R[0, 0] + R[1, 1] - R[2, 2],
+                  1 - R[0, 0] - R[1, 1] + R[2, 2]])
+    k = int(np.argmax(t))
+    s = 2 * np.sqrt(t[k])
+    q = [np.array([s / 4, (R[2, 1] - R[1, 2]) / s, (R[0, 2] - R[2, 0]) / s, (R[1, 0] - R[0, 1]) / s]),
+         np.array([(R[2, 1] - R[1, 2]) / s, s / 4, (R[0, 1] + R[1, 0]) / s, (R[0, 2] + R[2, 0]) / s]),
+         np.array([(R[0, 2] - R[2, 0]) / s, (R[0, 1] + R[1, 0]) / s, s / 4, (R[1, 2] + R[2, 1]) / s]),
+         np.array([(R[1, 0] - R[0, 1]) / s, (R[0, 2] + R[2, 0]) / s, (R[1, 2] + R[2, 1]) / s, s / 4])][k]
+    q = q / np.linalg.norm(q)
+    return -q if q[0] < 0 else q
+
+
 def qvec2rotmat(q):
     """Rotation of the unit quaternion (w, x, y, z) (COLMAP's convention: world -> camera)."""
     w, x, y, z = [float(v) for v in q]

@@ -20,6 +20,7 @@
 // and its gathers hit neighbouring triangles.
 #include "../../include/neuconw_hip.h"
 #include "ncw_common.h"
+#include "ncw_philox.h"  // philox4x32_10
 
 // the products and sums below are rounded one by one (no fused multiply-add): the restatement in tests/_surf_ref.py is then
 // the same arithmetic, and the result does not depend on what the compiler chooses to contract
@@ -84,23 +85,6 @@ __global__ __launch_bounds__(kBlock) void surf_pick_kernel(const double* __restr
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     tri[i] = surf_pick(cdf, n_faces, x[i]);
-}
-
-// Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11): counter c[4], key k[2] -> c[4]
-__device__ __forceinline__ void philox4x32_10(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0];
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-        c[0] = n0;
-        c[1] = (uint32_t)p1;
-        c[2] = n2;
-        c[3] = (uint32_t)p0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
 }
 
 __global__ __launch_bounds__(kBlock) void surf_sample_kernel(const double* __restrict__ verts, const int32_t* __restrict__ faces,
