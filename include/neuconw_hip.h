@@ -1601,6 +1601,72 @@ int ncw_synth_shade(const float* depth_ss, const int32_t* face_ss, const NcwSynt
 int ncw_synth_observe(const double* pts, const double* nrm, const int64_t* index, int64_t n, const NcwSynthView* view,
                       const float* depth, double* xy, double* err2, uint8_t* vis, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Depth and normal maps against ground truth (csrc/ncw_depthmetrics.hip; depthmetrics.compare_planes): the 2-D scores of ONE
+ * view -- abs-rel, RMSE, delta < 1.25^k, angular error and its shares, per-view completeness -- from two device planes, in one
+ * launch plus one fold.  THE REFERENCE HAS NO SUCH EVALUATION: the rules below are this project's, and no parity with any
+ * published depth benchmark's script is claimed.  Restated in numpy by tests/_depthmetrics_ref.py.
+ * ALL PER-PIXEL ARITHMETIC IS FLOAT32, EVERY OPERATION ROUNDED ONCE (no fused multiply-add, IEEE division and square root).  No
+ * float atomics: bitwise reproducible.  The kernel calls no transcendental function: thresholds and edge tables come from the
+ * host.  Pixel i = row * width + col; n = height * width.
+ *  1 INPUTS         gt_z [n] f32 (eye-space z, 0 = empty), gt_n [3][n] f32 unit normals or NULL, pred [n] f32, pred_n [3][n] f32 or
+ *                   NULL, mask [n] uint8 or NULL (non-zero = the pixel takes no part).
+ *                   mode NCW_DM_PRED_Z: pred is an eye-space z plane (z_p = pred), pred_n holds normals.
+ *                   mode NCW_DM_PRED_T: pred is views.trace_view's `depth` (t along the unit ray, unit-sphere units) and pred_n its
+ *                   encoded `normal` plane, decoded as 2 v - 1;  z_p = (t * scale) / nrm  with nrm = |d| of ncw_view_rays'
+ *                   un-normalised direction of the pixel (ncw_raymath.h, evaluated under rule "rounded once"; its camera-space
+ *                   z is -1, so z_p is the eye-space depth of the hit) and scale = the renderer's radius.
+ *  2 VALID          gt: gt_z finite and > 0.  prediction: pred finite and > 0 (PRED_T: and z_p finite and > 0).
+ *  3 CLASSES        A masked pixel counts as `masked` and nothing else.  Every other pixel is exactly one of both / gt_only
+ *                   (the surface is missing here) / pred_only (surface where the truth has none) / neither.
+ *  4 TERMS (both)   e = z_p - z_g,  a = |e|,  r = a / z_g,  q = max(z_p / z_g, z_g / z_p),  ee = e e,  s = ee / z_g.
+ *                   float64 sums 0..4 += a, e, ee, r, s (each formed in float32, then widened).  delta_k += (q < delta_thr[k]).
+ *                   hist_rel[b] += 1 with b = the number of rel_edges <= r (rel_edges [NR] f32, strictly ascending; b in 0..NR).
+ *  5 NORMALS        Scored on `both` pixels when gt_n and pred_n are given and both (decoded) normals are finite in every
+ *                   component and not (0, 0, 0):  dot = (x x' + y y') + z z',  c = dot < -1 ? -1 : (dot > 1 ? 1 : dot)  (a NaN dot,
+ *                   which takes overflowing products, stays NaN).  float64 sum 5 += c, normal count += 1, ang_k += (c >=
+ *                   cos_thr[k]), hist_cos[b] += 1 with b = the number of cos_edges > c (cos_edges [NA] f32, strictly descending;
+ *                   with edges cos(k D), k = 1..NA, that is floor(angle / D) off the edges: bin k holds the angles in (k D, (k + 1) D],
+ *                   bin 0 also the angle 0).
+ *  6 PLANES         optional outputs [n] f32: err_rel = r (NaN where not both), err_cos = c (NaN where not scored), z_pred = z_p
+ *                   where the prediction is valid, else 0 (masked pixels included).
+ *  7 ORDER          L = NCW_DM_LANES lanes, B = NCW_DM_BLOCK pixels per block, ceil(n / B) blocks.  Block b, lane l adds the terms
+ *                   of the pixels b B + j L + l, j = 0 .. B / L - 1, in ascending j, each sum on its own from 0.0; then the LANE
+ *                   TREE and the FOLD of ncw_align_sums (rule 6 there), word for word.  Counts and histograms are integers.
+ *  8 ROW            row v of table [V][K] (8-byte words), K = NCW_DM_FIXED + (NR + 1) + (NA + 1):  words 0..5 the float64 sums
+ *                   (a, e, ee, r, s, c) as bit patterns;  6..10 int64 both, gt_only, pred_only, neither, masked;  11..13 delta_1..3;
+ *                   14 normal count;  15..17 ang_1..3;  then hist_rel [NR + 1], then hist_cos [NA + 1] (int64).  The entry point
+ *                   zeroes the histogram words of row v on the stream; no other row is touched.
+ *   ncw_depthmetrics_scratch_bytes : bytes of scratch for a view of n_pix pixels (8-byte aligned; contents need no initialisation).
+ *   ncw_depthmetrics_view          : rules 1-8.  prm: HOST struct; its two tables are DEVICE pointers.
+ * Returns NCW_E_BADARG without a launch for a NULL gt_z / pred / prm / scratch / table / edge table, height or width < 1, row
+ * < 0, another mode, NA or NR outside 1..NCW_DM_MAX_EDGES, row_words != K, scale not finite and > 0, misaligned scratch / table,
+ * or (PRED_T) a camera whose size is not the planes'.
+ * ---------------------------------------------------------------------------------------- */
+#define NCW_DM_PRED_Z 0
+#define NCW_DM_PRED_T 1
+#define NCW_DM_LANES 256
+#define NCW_DM_BLOCK 2048
+#define NCW_DM_SUMS 6
+#define NCW_DM_COUNTS 12
+#define NCW_DM_FIXED 18
+#define NCW_DM_MAX_EDGES 2048
+typedef struct NcwDepthMetricsParams {
+    NcwViewCamera cam;      /* NCW_DM_PRED_T only: fx, fy, cx, cy, c2w, width, height (near / far unused) */
+    float scale;
+    float delta_thr[3];     /* 1.25, 1.25^2, 1.25^3 rounded to float32 by the caller */
+    float cos_thr[3];       /* cos of 11.25, 22.5, 30 degrees likewise */
+    int32_t n_cos_edges;    /* NA */
+    int32_t n_rel_edges;    /* NR */
+    int32_t _pad;
+    const float* cos_edges; /* device, [NA] */
+    const float* rel_edges; /* device, [NR] */
+} NcwDepthMetricsParams;
+int64_t ncw_depthmetrics_scratch_bytes(int64_t n_pix);
+int ncw_depthmetrics_view(const float* gt_z, const float* gt_n, const float* pred, const float* pred_n, const uint8_t* mask,
+                          int height, int width, int mode, const NcwDepthMetricsParams* prm, void* scratch, int64_t* table,
+                          int64_t row, int64_t row_words, float* err_rel, float* err_cos, float* z_pred, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,8 @@ def main(argv=None):
                  "   # the true mesh: recall 1" % (out, out, out),
                  "python scripts/render_view.py --cfg_path %s/train.yaml --ckpt_path <checkpoint> --sfm_path sparse [--surface]" % out,
                  "python scripts/surface_cloud.py --cfg_path %s/train.yaml --ckpt_path <checkpoint> --sfm_path sparse --max_views 16" % out,
+                 "python scripts/eval_depth.py --root_dir %s --gt_mesh %s/mesh.ply --pred_mesh <extracted mesh> | --cfg_path %s/train.yaml "
+                 "--ckpt_path <checkpoint>   # depth / normal maps per view against the true mesh" % (out, out, out),
                  "python scripts/estimate_sfm2gt.py --data_dir %s --gt_pcd_path %s/gt.ply   # the answer is in config.yaml and truth.json" % (out, out)):
         print("  " + line)
 
