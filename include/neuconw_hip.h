@@ -769,6 +769,40 @@ int ncw_knn_pca(const float* pts, const float* ref, int64_t m, const int32_t* id
 
 
 /* ------------------------------------------------------------------------------------------
+ * Implicit-moving-least-squares (IMLS) values of an oriented cloud on a sparse lattice: an all-within-R gather over the grid
+ * above (csrc/ncw_imls.hip; cloudmesh.py meshes a cloud with it).  The file is built without a * b + c -> fma contraction: every
+ * operation named below rounds once.
+ *   ncw_imls_values: the tables of a built grid -- pts_sorted [m][4] f32 (x, y, z, index bits) and cell_range -- the grid and its
+ *                  margin; nrm_sorted [m][4] f32: the normal of pts_sorted[i] in (x, y, z) of row i (the caller gathers them
+ *                  through the index in pts_sorted.w; .w is not read); blocks [nb][3] int32: coordinates of 4 x 4 x 4 blocks of
+ *                  lattice points; the lattice lat_lo[3], voxel, side[3] (lat_lo and side are HOST pointers, read by this
+ *                  entry); radius.  Row b * 64 + ((a * 4 + c) * 4 + e) of value [nb*64] f32, count [nb*64] int32 and d2min
+ *                  [nb*64] f32 belongs to the lattice point (i_x, i_y, i_z) = (4 bx + a, 4 by + c, 4 bz + e).
+ *                  x_a = lat_lo_a + float(i_a) * voxel in float32; r2 = radius * radius (one float32 product, formed by this
+ *                  entry); inv_r2 = 1.0 / double(r2).  The admitted set of a lattice point: every i in [0, m), over ALL of P in
+ *                  ascending pts_sorted order, with d2 <= r2 (inclusive), d2 = dx*dx + dy*dy + dz*dz in float32 summed left to
+ *                  right, dx = P[i].x - x.x (the expression of the 1-NN kernels).  In that order, in float64:
+ *                  t = 1 - double(d2) * inv_r2; w = (t * t) * (t * t); g = -((dx * nx + dy * ny) + dz * nz); S += w * g; W += w.
+ *                  count = the number admitted; d2min = the smallest admitted d2, +inf when count = 0; value = float(S / W)
+ *                  when count > 0 and W > 0, else NaN (a lone point exactly at d2 == r2 has w = 0: NaN).  A lattice index
+ *                  outside [0, side) (a negative block coordinate included) writes NaN / 0 / +inf.  A point of P with a
+ *                  non-finite coordinate is never admitted.
+ *                  One wave per block: it walks the cells of its block's box grown by radius (1 + 2^-20) + margin, clamped to
+ *                  the grid (the boundary cells hold the clamped outliers; the kernel's header argues that this is a superset
+ *                  of what d2 <= r2 can admit), in cell order, and stages their points through LDS; every lane tests every
+ *                  staged point.  No atomics, no transcendental function, no square root: the outputs are a function of the
+ *                  inputs only, bitwise reproducible and the same for any order or split of `blocks` into launches.
+ *                  work [nb] int32 or NULL: the points staged per block (measurement only).
+ *                  NCW_E_BADARG without a launch for a NULL pointer (work excepted), a bad grid, m outside [1, 2^31), voxel <= 0,
+ *                  infinite or NaN, radius <= 0 or NaN or with r2 not a finite normal number, margin < 0, infinite or NaN, a side
+ *                  outside 1 .. 16384, nb >= 2^25; 0 without a launch for nb <= 0.
+ * ---------------------------------------------------------------------------------------- */
+int ncw_imls_values(const float* pts_sorted, const float* nrm_sorted, const int32_t* cell_range, int64_t m, const NcwNnGrid* grid,
+                    float margin, const int32_t* blocks, int64_t nb, const float* lat_lo, float voxel, const int32_t* side,
+                    float radius, float* value, int32_t* count, float* d2min, int32_t* work, void* stream);
+
+
+/* ------------------------------------------------------------------------------------------
  * Triangle depth rasterizer of the reprojection visibility filter: replaces the pyrender depth render of
  * utils/pyrender_renderer.py:16-24 (utils/reproj_filter.py:208), the back-projection `reproject` of
  * utils/reproj_filter.py:133-152 and the per-pixel open3d KD-tree marking loop of :229-232 (with ncw_nn_*).

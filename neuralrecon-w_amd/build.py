@@ -34,9 +34,10 @@ MLP_FILES = {"ncw_pp.hip"}
 # ncw_knn.hip: the k-NN kernel's d2 and the PCA's float64 sequence likewise (tests/_knn_ref.py).
 # ncw_synth.hip: the shading and observation passes of the synthetic scenes likewise (tests/_synth_ref.py).
 # ncw_depthmetrics.hip: the per-pixel terms of the depth / normal scores likewise (tests/_depthmetrics_ref.py).
+# ncw_imls.hip: the float32 admission test and the float64 weighted sums of the IMLS values likewise (tests/_imls_ref.py).
 FILE_FLAGS = {"ncw_gtreproj.hip": ["-fno-slp-vectorize"], "ncw_trace.hip": ["-ffp-contract=off"],
               "ncw_knn.hip": ["-ffp-contract=off"], "ncw_synth.hip": ["-ffp-contract=off"],
-              "ncw_depthmetrics.hip": ["-ffp-contract=off"]}
+              "ncw_depthmetrics.hip": ["-ffp-contract=off"], "ncw_imls.hip": ["-ffp-contract=off"]}
 if TAG and "NCW_MLP_FLAGS" in os.environ:  # A/B probe builds (scripts/): e.g. NCW_MLP_FLAGS="" NCW_BUILD_TAG=plain
     MLP_FLAGS = os.environ["NCW_MLP_FLAGS"].split()
 # second flag group (A/B probe builds only): NCW_FLAGS2 applied to the files listed in NCW_FILES2

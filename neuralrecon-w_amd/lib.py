@@ -15,7 +15,7 @@ PREC_BF16 = 1
 PREC_F16 = 2  # fp16 operands, f32 accumulate; backward needs the loss scale (renderer.grad_scale)
 MAX_LAYERS = 12
 MAX_SEGS = 4
-ABI_VERSION = 40  # 40: per-view depth / normal scores against ground truth (ncw_depthmetrics_view / _scratch_bytes, NcwDepthMetricsParams);  39: synthetic scenes (ncw_synth_shade / ncw_synth_observe, NcwSynthMaterial, NcwSynthImage, NcwSynthView);  38: k nearest neighbours and per-point PCA (ncw_knn_query / ncw_knn_pca);  37: surface-cloud fusion (ncw_fuse_insert / _move / _resolve, NcwFuseGrid, NcwFuseTable);  36: sphere tracing (ncw_trace_begin / _step / _finish / _store / _scratch_bytes);  35: nearest point within a radius (ncw_nn_coarse / ncw_nn_query_within);  34: marching cubes on brick-blocked sparse values (ncw_mcs_neighbors / _count / _cube_ids / _emit);  33: sfm2gt estimation (ncw_align_transform / ncw_align_sums / ncw_align_sums_blocks);  32: mesh simplification (ncw_mesh_sc_keys / _sc_faces / _sc_place);  31: ray source (ncw_source_batch, NcwSourceRec, NcwSourceImage);  30: mesh operations (ncw_mesh_cc_hook / _cc_flatten / _cc_sizes / _face_select / _compact_mark / _compact_faces);  29: appearance-code fit on frozen geometry (ncw_appfit_loss / ncw_appfit_step / ncw_appfit_step_scratch_floats);  28: floor-normal loss (NcwCompositeGrad.d_normals, ncw_ray_floor_fwd / _bwd);  27: exact point-to-triangle-mesh distances of the mesh evaluation (ncw_ptm_pack / _count / _emit / _ranges / _cell_keys / _query / _brute, NcwPtmGrid);  26: ground-truth reprojection error of SfM tracks (ncw_pixel_nearest / ncw_reproj_errors, NcwPixelQuery);  25: view selection of the split writer (ncw_views_roi);  24: voxel first-hit views of the reprojection filter's point-cloud source (ncw_voxel_view_seen / ncw_voxel_points_seen, NcwVoxelView);  23: area-weighted surface sampling of the mesh evaluation (ncw_surf_weights / ncw_surf_pick / ncw_surf_sample);  22: ray cache rows (ncw_sfm_depth_splat / ncw_cache_rows, NcwCacheOctree);  21: camera views (ncw_view_rays / ncw_view_store / ncw_image_minmax / ncw_depth_colormap / ncw_image_sqerr / ncw_image_ssim, NcwViewCamera);  20: triangle depth rasterizer of the reprojection filter (ncw_raster_small / _large / _resolve / _backproject / _mark, NcwRasterView);  19: exact 1-NN of the mesh evaluation (ncw_nn_cell_keys / ncw_nn_cell_ranges / ncw_nn_query / ncw_nn_brute, NcwNnGrid);  18: NcwSdfStash.s = residuals of h (adj_mode 2), NcwSdfNet.adj_mode, NcwColorNet.act_split;  17: ncw_ray_voxel_trace (all ray / voxel intersections: kaolin's unbatched_raytrace contract);  16: NcwSdfNet.wt_lo (adjoint sweep with hi + lo weights), NcwNerfNet.w_*_lo;  15: forward-only render form of ncw_sdf_fwd / ncw_color_fwd / ncw_nerf_fwd (NULL stash members);  14: NcwColorNet.w_*_lo (split colour weights, forward);  13: NcwNerfStash.aux_bias;  12: ncw_aux_ray_bias, NcwColorStash.aux_bias, ncw_source_hash;  11: marching cubes (ncw_mc_count / ncw_mc_emit replace the marching-tetrahedra entry points);  10: split-precision SDF value path (NcwSdfNet.w_lo, NcwPackDesc.residual);  9: device-resident optimiser state (ncw_adam_step_dev, NcwAdamState), dynamic loss scale (grad_scale_dev / grad_mul_dev);  8: NcwPoints mode 4 (idx / count), NcwWgradDesc.n_points_dev, ncw_bg_select;  7: fp16 (prec 2), grad_scale / grad_mul;  6: ray prologue / inv_s / loss launches, NcwCompositeOut.weights_max;  5: ncw_scatter_add_rows;  4: ncw_batch_assemble;  3: ordered fp32 wgrad, d_a_rows / ncw_ray_sum_rows, per-ray d_inv_s;  2: 2: NcwWgradDesc.ksplit/n_points, NcwCompositeIn.cos_anneal_dev, ray tail / mesh / optimiser entry points
+ABI_VERSION = 41  # 41: IMLS values of an oriented cloud on a sparse lattice (ncw_imls_values);  40: per-view depth / normal scores against ground truth (ncw_depthmetrics_view / _scratch_bytes, NcwDepthMetricsParams);  39: synthetic scenes (ncw_synth_shade / ncw_synth_observe, NcwSynthMaterial, NcwSynthImage, NcwSynthView);  38: k nearest neighbours and per-point PCA (ncw_knn_query / ncw_knn_pca);  37: surface-cloud fusion (ncw_fuse_insert / _move / _resolve, NcwFuseGrid, NcwFuseTable);  36: sphere tracing (ncw_trace_begin / _step / _finish / _store / _scratch_bytes);  35: nearest point within a radius (ncw_nn_coarse / ncw_nn_query_within);  34: marching cubes on brick-blocked sparse values (ncw_mcs_neighbors / _count / _cube_ids / _emit);  33: sfm2gt estimation (ncw_align_transform / ncw_align_sums / ncw_align_sums_blocks);  32: mesh simplification (ncw_mesh_sc_keys / _sc_faces / _sc_place);  31: ray source (ncw_source_batch, NcwSourceRec, NcwSourceImage);  30: mesh operations (ncw_mesh_cc_hook / _cc_flatten / _cc_sizes / _face_select / _compact_mark / _compact_faces);  29: appearance-code fit on frozen geometry (ncw_appfit_loss / ncw_appfit_step / ncw_appfit_step_scratch_floats);  28: floor-normal loss (NcwCompositeGrad.d_normals, ncw_ray_floor_fwd / _bwd);  27: exact point-to-triangle-mesh distances of the mesh evaluation (ncw_ptm_pack / _count / _emit / _ranges / _cell_keys / _query / _brute, NcwPtmGrid);  26: ground-truth reprojection error of SfM tracks (ncw_pixel_nearest / ncw_reproj_errors, NcwPixelQuery);  25: view selection of the split writer (ncw_views_roi);  24: voxel first-hit views of the reprojection filter's point-cloud source (ncw_voxel_view_seen / ncw_voxel_points_seen, NcwVoxelView);  23: area-weighted surface sampling of the mesh evaluation (ncw_surf_weights / ncw_surf_pick / ncw_surf_sample);  22: ray cache rows (ncw_sfm_depth_splat / ncw_cache_rows, NcwCacheOctree);  21: camera views (ncw_view_rays / ncw_view_store / ncw_image_minmax / ncw_depth_colormap / ncw_image_sqerr / ncw_image_ssim, NcwViewCamera);  20: triangle depth rasterizer of the reprojection filter (ncw_raster_small / _large / _resolve / _backproject / _mark, NcwRasterView);  19: exact 1-NN of the mesh evaluation (ncw_nn_cell_keys / ncw_nn_cell_ranges / ncw_nn_query / ncw_nn_brute, NcwNnGrid);  18: NcwSdfStash.s = residuals of h (adj_mode 2), NcwSdfNet.adj_mode, NcwColorNet.act_split;  17: ncw_ray_voxel_trace (all ray / voxel intersections: kaolin's unbatched_raytrace contract);  16: NcwSdfNet.wt_lo (adjoint sweep with hi + lo weights), NcwNerfNet.w_*_lo;  15: forward-only render form of ncw_sdf_fwd / ncw_color_fwd / ncw_nerf_fwd (NULL stash members);  14: NcwColorNet.w_*_lo (split colour weights, forward);  13: NcwNerfStash.aux_bias;  12: ncw_aux_ray_bias, NcwColorStash.aux_bias, ncw_source_hash;  11: marching cubes (ncw_mc_count / ncw_mc_emit replace the marching-tetrahedra entry points);  10: split-precision SDF value path (NcwSdfNet.w_lo, NcwPackDesc.residual);  9: device-resident optimiser state (ncw_adam_step_dev, NcwAdamState), dynamic loss scale (grad_scale_dev / grad_mul_dev);  8: NcwPoints mode 4 (idx / count), NcwWgradDesc.n_points_dev, ncw_bg_select;  7: fp16 (prec 2), grad_scale / grad_mul;  6: ray prologue / inv_s / loss launches, NcwCompositeOut.weights_max;  5: ncw_scatter_add_rows;  4: ncw_batch_assemble;  3: ordered fp32 wgrad, d_a_rows / ncw_ray_sum_rows, per-ray d_inv_s;  2: 2: NcwWgradDesc.ksplit/n_points, NcwCompositeIn.cos_anneal_dev, ray tail / mesh / optimiser entry points
 
 
 class NcwSeg(C.Structure):
@@ -260,6 +260,8 @@ _PROTOS = {
     "ncw_nn_query_within": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, _VP, C.c_int64, C.POINTER(NcwNnGrid), C.c_float, C.c_float, _VP, _VP, _VP]),
     "ncw_knn_query": (C.c_int, [_VP, _VP, _VP, C.c_int, _VP, _VP, _VP, C.c_int64, C.POINTER(NcwNnGrid), C.c_float, C.c_float, C.c_int, C.c_int, _VP, _VP, _VP, _VP, _VP]),
     "ncw_knn_pca": (C.c_int, [_VP, _VP, C.c_int64, _VP, _VP, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_float), _VP, _VP, _VP, _VP, _VP]),
+    "ncw_imls_values": (C.c_int, [_VP, _VP, _VP, C.c_int64, C.POINTER(NcwNnGrid), C.c_float, _VP, C.c_int64, C.POINTER(C.c_float), C.c_float,
+                                  C.POINTER(C.c_int32), C.c_float, _VP, _VP, _VP, _VP, _VP]),
     "ncw_raster_small": (C.c_int, [_VP, C.c_int64, _VP, C.c_int64, C.POINTER(NcwRasterView), _VP, _VP, _VP, _VP]),
     "ncw_raster_large": (C.c_int, [_VP, C.c_int64, _VP, C.POINTER(NcwRasterView), _VP, _VP, C.c_int64, _VP, _VP]),
     "ncw_raster_resolve": (C.c_int, [_VP, C.c_int64, _VP, _VP, _VP]),
